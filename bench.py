@@ -1,6 +1,7 @@
 """Benchmark: BASELINE.json's headline metric on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2]): Schmidl-Cox [A][A] float32 metric + CFO,
 N = 1024 (L = 512), cir1 multipath + AWGN + CFO, 65536 streams x 1024 complex64 samples per
@@ -15,9 +16,14 @@ own 65536-stream batch; "strong" splits --global-batch streams over the ranks
 (shard.shard_bounds).  Timing: barrier + synchronize on both sides of the K timed steps, MAX
 over ranks.
 
-Rank 0 prints one JSON line with `roofline` (dominant kernel vs HBM peak), `cpu_baseline`
-(C port of the reference loop + NumPy + literal Python loop on the host cores) and `parity`
-(every stream's events against the C oracle, oracle/parity.py criterion).
+A plain run sets up, warms up, times the K steps and rank 0 prints one JSON line: the headline
+`value` / `ms_per_step` and `roofline` (the timed kernel's algorithmic bytes over the same K steps
+vs HBM peak).  ``--dump-outputs DIR`` also writes what the last timed step left in the detector's
+result (P, R, M of a fixed seeded sample of streams; every stream's n_events, ev_int, ev_real) as
+DIR/<name>.npy; inputs are seeded, so two builds can be compared output for output.  ``--full``
+adds what takes runs of its own: `cpu_baseline` (C port of the reference loop + NumPy + literal
+Python loop on the host cores, the other configs' CPU rates) and `parity` (every stream's events
+against the C oracle, oracle/parity.py criterion).
 """
 from __future__ import annotations
 
@@ -60,13 +66,22 @@ def parse(argv=None):
     ap.add_argument("--placement", choices=("auto", "contiguous", "plain"), default="auto",
                     help="AABatchDetector placement of the detector's buffers (the product default "
                          "'auto'; the JSON line records the placement actually used)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (float32 / "
+                         "float64; P, R, M for a fixed seeded sample of streams, the event arrays whole)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and the every-stream parity check against the C oracle "
+                         "(cpu_baseline, parity); a plain run only times the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline / parity")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-budget", type=float, default=3.0, help="seconds per CPU leg")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launcher self-test on CPU (gloo, no HIP): exercises rank start-up, sharding, "
                          "barriers and MAX-of-times; prints the same JSON line with selftest=true")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.dump_outputs and a.selftest_cpu:
+        ap.error("--dump-outputs needs the HIP detector (not --selftest-cpu)")
+    return a
 
 
 # ------------------------------------------------------------------------------------------
@@ -266,6 +281,36 @@ def pmc_traffic(workload_key: str):
         return None
 
 
+DUMP_ROWS = 2048               # streams of P / R / M kept by --dump-outputs (16 KiB each: 32 MiB)
+DUMP_SEED = 20260                # which streams: a seeded choice, the same for every run of a shape
+
+
+def dump_outputs(res, out_dir: str, rank: int, world: int) -> None:
+    """Write the detector's result (what a caller of AABatchDetector.run receives) as .npy files:
+    P (complex -> trailing [re, im] axis), R, M for DUMP_ROWS seeded streams (`rows`, sorted), and
+    n_events, ev_int, ev_real of every stream up to 16 MiB per array.  float32 stays float32,
+    everything else is written as float64 (exact for the int32 counts and the int64 sample indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = res.n_events.shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_ROWS), replace=False))
+    ridx = torch.from_numpy(rows).to(res.n_events.device)
+    arrays = {"rows": rows.astype(np.float64)}
+    for name in ("P", "R", "M"):
+        t = getattr(res, name)
+        if t is None:
+            continue
+        t = t.index_select(0, ridx)
+        t = torch.view_as_real(t) if t.is_complex() else t
+        arrays[name] = t.cpu().numpy()
+    for name in ("n_events", "ev_int", "ev_real"):
+        t = getattr(res, name)
+        per = max(1, t.numel() // max(B, 1) * 8)            # bytes per stream once written as float64
+        arrays[name] = t[: max(1, (16 << 20) // per)].cpu().numpy().astype(np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(arr))
+
+
 class _SelftestDetector:
     """--selftest-cpu stand-in for the HIP detector: a rank-dependent sleep, so MAX-over-ranks
     is observable.  Never used without --selftest-cpu."""
@@ -377,6 +422,8 @@ def main(argv=None):
         return 0
 
     res = det.result
+    if a.dump_outputs:
+        dump_outputs(res, a.dump_outputs, rank, world)
     stored = int(torch.clamp(res.n_events, max=E).sum().item())
     alg_bytes = B * T * BYTES_PER_SAMPLE + B * BYTES_PER_STREAM + stored * BYTES_PER_EVENT
     launch_s = (ms / a.steps) / 1e3                       # this rank's average launch duration
@@ -389,7 +436,7 @@ def main(argv=None):
     out["events_per_stream"] = round(float(res.n_events.float().mean().item()), 3)
     out["host_wall_s"] = round(t_host, 4)
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(det, L, a.cpu_threads, a.cpu_budget)
         else:
             out["cpu_baseline"] = None

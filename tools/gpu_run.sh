@@ -7,7 +7,7 @@
 # gpurun_out/TAG_name.log) or one of the shorthands:
 #   tests        pytest -m gpu (thread timeouts, so a hang names its test)
 #   smoke        __graft_entry__.py smoke
-#   bench        python bench.py (the driver's default line)
+#   bench        python bench.py --full (headline + CPU baselines + every-stream parity)
 #   prof         rocprofv3 --kernel-trace --stats of bench.py (gpurun_out/TAG_prof/)
 #   pmcF / pmcW  FETCH_SIZE / WRITE_SIZE passes of bench.py (one counter group per pass)
 #   cfgs         tools/bench_configs.py (every secondary config)
@@ -43,7 +43,7 @@ for S in "$@"; do
     tests)  run tests 900 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     tests:*) run tests 900 python -u -m pytest ${S#tests:} -m gpu -q -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     smoke)  run smoke 300 python __graft_entry__.py smoke ;;
-    bench)  run bench 600 python bench.py ;;
+    bench)  run bench 600 python bench.py --full ;;
     prof)   run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o bench --output-format csv -- python3 bench.py --steps 20 --no-cpu-baseline ;;
     pmcF)   run pmcF 120 rocprofv3 --pmc FETCH_SIZE -d $OUT/${TAG}_pmcF -o bench --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline ;;
     pmcW)   run pmcW 120 rocprofv3 --pmc WRITE_SIZE -d $OUT/${TAG}_pmcW -o bench --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline ;;
