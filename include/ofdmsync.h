@@ -101,6 +101,9 @@ const char* ofs_status_string(int32_t status);
  *                cap; default 16384 for the one-antenna storing kernel = 10 per CU, 1 = no cap)
  *   OCC_LDS      n >= 0: bytes of unused dynamic LDS added to the other wave-per-stream launches
  *                (aa_stream, win_fast, aa_exact, rtl_exact, the fast back-end; occupancy A/B)
+ *   FAST_RMPAIR  0|1: R and M of two adjacent rows of the one-antenna E = 2 storing aa_fast kernel as
+ *                one 16-byte store per lane (one contiguous 1 KiB span per wave instruction; default 1)
+ *   FAST_ST_POLICY 0|1: that kernel's P/R/M stores plain / non-temporal (default 1)
  * ofs_debug_set_variant returns OFS_EINVAL for an unknown name; value OFS_VARIANT_UNSET clears
  * one variant, ofs_debug_reset_variants clears all.  The table is per calling thread
  * (thread_local): a variant set by one thread steers only the calls that same thread makes, and

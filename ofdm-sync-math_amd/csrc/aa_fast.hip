@@ -43,10 +43,7 @@ constexpr int FAST_WG = OFS_FAST_WG;   // one wave = one stream per workgroup (p
 constexpr int TMAX = 1024;        // stream length handled by the fast path
 constexpr int FAST_CAP_LDS = 160 * 1024 / 10;   // occupancy cap of the storing kernel: 10 workgroups per CU (launch)
 
-// cache policy knobs (tuning builds): non-temporal output stores, LDS-DMA aux bits
-#ifndef OFS_STORE_NT
-#define OFS_STORE_NT 0
-#endif
+// cache policy knob (tuning builds): LDS-DMA aux bits
 #ifndef OFS_DMA_AUX
 #define OFS_DMA_AUX 0
 #endif
@@ -65,19 +62,45 @@ __device__ __forceinline__ pf2 mulc_acc(pf2 c, pf2 d, pf2 acc) {
     acc = __builtin_elementwise_fma(c, d.xx, acc);
     return __builtin_elementwise_fma(c.yx, pf2{d.y, -d.y}, acc);
 }
+// Output stores of the storing kernel (P, R, M; event stores stay plain).  SP = cache policy of the
+// store: 0 plain, 1 non-temporal (variant FAST_ST_POLICY; the default of the headline kernel, launch()).
+template <int SP>
 __device__ __forceinline__ void st_out(float4* p, float4 v) {
-#if OFS_STORE_NT
-    __builtin_nontemporal_store(nf4{v.x, v.y, v.z, v.w}, reinterpret_cast<nf4*>(p));
-#else
-    *p = v;
-#endif
+    const nf4 d = nf4{v.x, v.y, v.z, v.w};
+    if constexpr (SP == 1) __builtin_nontemporal_store(d, reinterpret_cast<nf4*>(p));
+    else *p = v;
 }
+template <int SP>
 __device__ __forceinline__ void st_out(float2* p, float2 v) {
-#if OFS_STORE_NT
-    __builtin_nontemporal_store(nf2{v.x, v.y}, reinterpret_cast<nf2*>(p));
-#else
-    *p = v;
-#endif
+    const nf2 d = nf2{v.x, v.y};
+    if constexpr (SP == 1) __builtin_nontemporal_store(d, reinterpret_cast<nf2*>(p));
+    else *p = v;
+}
+
+// Row-paired R / M store (E = 2): rows k, k+1 of one stream are 256 consecutive floats (1 KiB) of the
+// buffer.  Lane l holds (a[0], a[1]) = floats 2l, 2l+1 of row k and (b[0], b[1]) of row k+1; it stores
+// floats [4l, 4l+4) of the span - the values of lanes 2(l & 31), 2(l & 31) + 1 of row k + (l >= 32) -
+// as one float4, so the wave instruction writes one contiguous 1 KiB span in lane order.  The move:
+// a quad-perm DPP packs what the even (odd) source lanes hand over into one register - even lanes
+// keep row k's value, odd lanes take row k+1's from the lane below (above) - then one ds_bpermute per
+// output dword with the same index for all four.  No LDS allocation, no barrier; all 64 lanes active.
+template <int SP>
+__device__ __forceinline__ void st_rows2(float* span, const float (&a)[2], const float (&b)[2], int lane) {
+    const bool odd = (lane & 1) != 0;
+    const int idx = (lane < 32 ? 2 * lane : 2 * lane - 63) * 4;
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int ai = __float_as_int(a[e]), bi = __float_as_int(b[e]);
+        // the DPP moves run with every lane active (before the selects, not inside a ?: arm)
+        const int bdn = dpp_i<0xA0>(bi);                        // quad_perm:[0,0,2,2]: lane 2i+1 <- b of lane 2i
+        const int aup = dpp_i<0xF5>(ai);                        // quad_perm:[1,1,3,3]: lane 2i <- a of lane 2i+1
+        const int we = odd ? bdn : ai;
+        const int wo = odd ? bi : aup;
+        o[e] = __int_as_float(__builtin_amdgcn_ds_bpermute(idx, we));
+        o[2 + e] = __int_as_float(__builtin_amdgcn_ds_bpermute(idx, wo));
+    }
+    st_out<SP>(reinterpret_cast<float4*>(span) + lane, make_float4(o[0], o[1], o[2], o[3]));
 }
 
 
@@ -106,9 +129,13 @@ __device__ __forceinline__ void st_out(float2* p, float2 v) {
 #define OFS_FAST_GATE_LATE 0
 #endif
 // DO: detect-only instantiation (P/R/M/valid not stored, events only: SURVEY §8d); S32: fp32
-// row scans (ofs_common.h row_scan; the detect-only default, issue-bound there)
-template <int E, int MR, int NA, bool DO, bool S32>
+// row scans (ofs_common.h row_scan; the detect-only default, issue-bound there); SV: store path of
+// the one-antenna E = 2 storing kernel = 2 * (row-paired R/M stores) + (non-temporal stores, st_out)
+template <int E, int MR, int NA, bool DO, bool S32, int SV = 0>
 __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
+    static_assert(SV == 0 || (E == 2 && NA == 1 && !DO), "store-path variants: one-antenna E = 2 storing kernel");
+    constexpr int SP = SV & 1;                 // output store cache policy
+    constexpr bool RP = (SV & 2) != 0;         // R/M of rows k, k+1 (k even) as one 16-byte store per lane
     constexpr int RL = 64 * E;                 // samples per row
     constexpr int RW = TMAX / RL;              // rows per stream
     constexpr int L = MR * RL;
@@ -147,7 +174,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
         }
     auto ldrow = [&](int t, int k, int j) { return lds[w][(t * RW + k) * V4 + j][lane]; };
     // SPR counts only when all of P, R, M are stored (uncounted stores only make the wait longer)
-    const bool all_out = !DO && a.P && a.R && a.M;
+    const bool all_out = !DO && !RP && a.P && a.R && a.M;      // (paired R/M stores: not counted)
     auto row_wait = [&](int k) {
         if (all_out) ofs::vmcnt_wait((RW - 1 - k) * NA * V4 + k * SPR);
         else ofs::vmcnt_wait((RW - 1 - k) * NA * V4);
@@ -175,7 +202,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                 asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xreg[t][k][j]) : "v"(xs + n) : "memory");
             }
         }
-    const bool count_st = !DO && a.P && a.R && a.M && T == TMAX;
+    const bool count_st = !DO && !RP && a.P && a.R && a.M && T == TMAX;
     auto ldrow = [&](int t, int k, int j) { const nf4 v = xreg[t][k][j]; return make_float4(v.x, v.y, v.z, v.w); };
     auto row_wait = [&](int k) {
         if (count_st) ofs::vmcnt_wait((RW - 1 - k) * NA * V4 + k * SPR);
@@ -234,6 +261,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     float* Rout = DO ? nullptr : reinterpret_cast<float*>(a.R);
     float* Mout = DO ? nullptr : reinterpret_cast<float*>(a.M);
     const float floor_ = 1e-6f * (float)L;
+    float hR[2] = {0.f, 0.f}, hM[2] = {0.f, 0.f};   // RP: R, M of the even row, held for one row
 
 #pragma unroll
     for (int k = 0; k < RW; ++k) {
@@ -297,24 +325,41 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
             }
 
             const int64_t o = b * a.T + nb;
+            // row-paired R/M stores (st_rows2): rows k0 = k & ~1 and k0 + 1 go out together from the odd
+            // row when both lie entirely inside the stream and T % 4 == 0 (the span b*T + RL*k0 is then
+            // 16-byte aligned and ends inside the stream); every other row stores its own float2
+            // (wave-uniform choice)
+            const bool paired = RP && (T & 3) == 0 && RL * ((k & ~1) + 2) <= T;
 #pragma unroll
             for (int j = 0; j < V4; ++j) {
                 if (nb + 2 * j < T) {
-                    if (Pout) st_out(reinterpret_cast<float4*>(Pout + 2 * (o + 2 * j)),
-                                    make_float4(pf[2 * j][0], pf[2 * j][1], pf[2 * j + 1][0], pf[2 * j + 1][1]));
+                    if (Pout) st_out<SP>(reinterpret_cast<float4*>(Pout + 2 * (o + 2 * j)),
+                                         make_float4(pf[2 * j][0], pf[2 * j][1], pf[2 * j + 1][0], pf[2 * j + 1][1]));
                     // float4 R/M stores need T % 4 == 0: otherwise the last pair of a stream
                     // would spill into the next stream's first samples (and b*T+nb is not
                     // 16-byte aligned for odd b)
-                    if (E % 4 != 0 || (T & 3) != 0) {
-                        if (Rout) st_out(reinterpret_cast<float2*>(Rout + o + 2 * j), make_float2(rf[2 * j], rf[2 * j + 1]));
-                        if (Mout) st_out(reinterpret_cast<float2*>(Mout + o + 2 * j), make_float2(mf[2 * j], mf[2 * j + 1]));
+                    if (paired) {                               // R/M of this row: st_rows2 below
+                    } else if (E % 4 != 0 || (T & 3) != 0) {
+                        if (Rout) st_out<SP>(reinterpret_cast<float2*>(Rout + o + 2 * j), make_float2(rf[2 * j], rf[2 * j + 1]));
+                        if (Mout) st_out<SP>(reinterpret_cast<float2*>(Mout + o + 2 * j), make_float2(mf[2 * j], mf[2 * j + 1]));
                     } else if ((j & 1) == 0) {
-                        if (Rout) st_out(reinterpret_cast<float4*>(Rout + o + 2 * j),
-                                        make_float4(rf[2 * j], rf[2 * j + 1], rf[2 * j + 2], rf[2 * j + 3]));
-                        if (Mout) st_out(reinterpret_cast<float4*>(Mout + o + 2 * j),
-                                        make_float4(mf[2 * j], mf[2 * j + 1], mf[2 * j + 2], mf[2 * j + 3]));
+                        if (Rout) st_out<SP>(reinterpret_cast<float4*>(Rout + o + 2 * j),
+                                             make_float4(rf[2 * j], rf[2 * j + 1], rf[2 * j + 2], rf[2 * j + 3]));
+                        if (Mout) st_out<SP>(reinterpret_cast<float4*>(Mout + o + 2 * j),
+                                             make_float4(mf[2 * j], mf[2 * j + 1], mf[2 * j + 2], mf[2 * j + 3]));
                     }
                     if (!DO && a.valid) { a.valid[o + 2 * j] = (k >= MR); a.valid[o + 2 * j + 1] = (k >= MR); }
+                }
+            }
+            if constexpr (RP) {
+                if (paired) {
+                    if ((k & 1) == 0) {
+                        hR[0] = rf[0]; hR[1] = rf[1]; hM[0] = mf[0]; hM[1] = mf[1];
+                    } else {
+                        const int64_t o0 = b * a.T + RL * (k - 1);
+                        if (Rout) st_rows2<SP>(Rout + o0, hR, rf, lane);
+                        if (Mout) st_rows2<SP>(Mout + o0, hM, mf, lane);
+                    }
                 }
             }
 
@@ -682,6 +727,24 @@ int launch(const AaFastArgs& a, hipStream_t st) {
     // overrides (1: no cap, A/B).
     const int64_t pad = ofs::variant_or(ofs::V_FAST_LDS, (!det_only && NA == 1) ? FAST_CAP_LDS : 0);
     const size_t shm = pad > 0 && pad <= 65536 ? (size_t)pad : 0;
+    // store path of the one-antenna E = 2 storing kernel with fp64 scans (the headline): row-paired
+    // 16-byte R/M stores and non-temporal P/R/M stores.  Paired on the same buffers, 3 fresh allocations x
+    // 11 rotated repetitions, against plain float2 stores (profiles/headline_store_path_arms.jsonl; A/A
+    // spread 0.04 %): pairing alone -0.3..-1.0 %, non-temporal alone -6.7..-7.9 %, both -8.1..-9.3 %
+    // (0.2805-0.2834 -> 0.2571-0.2584 ms); write-through forms (sc1, sc0 sc1) within +-0.1 % of plain,
+    // removed.  Variants FAST_RMPAIR = 0 | 1, FAST_ST_POLICY = 0 | 1 override (tests: bit-identity).
+    if constexpr (E == 2 && NA == 1) {
+        if (!det_only && !s32) {
+            const int sv = (ofs::variant_or(ofs::V_FAST_RMPAIR, 1) != 0 ? 2 : 0) | (ofs::variant_or(ofs::V_FAST_ST_POLICY, 1) == 1 ? 1 : 0);
+            switch (sv) {
+                case 0: hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 0>), grid, blk, shm, st, a); break;
+                case 1: hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 1>), grid, blk, shm, st, a); break;
+                case 2: hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 2>), grid, blk, shm, st, a); break;
+                default: hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3>), grid, blk, shm, st, a);
+            }
+            return hipGetLastError() == hipSuccess ? 1 : OFS_EHIP;
+        }
+    }
     if (det_only && s32) hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, true, true>), grid, blk, shm, st, a);
     else if (det_only) hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, true, false>), grid, blk, shm, st, a);
     else if (s32) hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, true>), grid, blk, shm, st, a);
