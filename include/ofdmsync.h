@@ -104,6 +104,8 @@ const char* ofs_status_string(int32_t status);
  *   FAST_RMPAIR  0|1: R and M of two adjacent rows of the one-antenna E = 2 storing aa_fast kernel as
  *                one 16-byte store per lane (one contiguous 1 KiB span per wave instruction; default 1)
  *   FAST_ST_POLICY 0|1: that kernel's P/R/M stores plain / non-temporal (default 1)
+ *   FAST_HEAD    0: ofs_aa_detect_ex ignores OFS_AA_HEAD_RESIDENT (the P/M head is rewritten; A/B of
+ *                both arms on the same buffers)
  * ofs_debug_set_variant returns OFS_EINVAL for an unknown name; value OFS_VARIANT_UNSET clears
  * one variant, ofs_debug_reset_variants clears all.  The table is per calling thread
  * (thread_local): a variant set by one thread steers only the calls that same thread makes, and
@@ -129,6 +131,25 @@ int32_t ofs_aa_detect(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant, i
                       int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
                       int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
                       void* stream);
+
+/*
+ * ofs_aa_detect with flags; ofs_aa_detect is the flags = 0 call.  Unknown flag bits: OFS_EINVAL.
+ *
+ * OFS_AA_HEAD_RESIDENT: the caller guarantees that P[b][n] and M[b][n] already hold +0.0 (all-zero
+ * bits) for every b and every n < min(L, T).  Those elements are constant by the algorithm's
+ * definition - the delay line is not yet valid there, so P[n] = M[n] = +0.0 for any input, NaN and
+ * Inf included - and a caller that reuses its output buffers from call to call still holds them.
+ * The library may then leave them unwritten (it may also still write zeros there); every n >= L is
+ * written exactly as without the flag, and R, valid, the events and n_events are unaffected.  A
+ * permission, not an obligation: the fp32 fast paths (ofs_aa_plan 1000-1199) use it, every other
+ * plan (general engine, integer-exact / fp64 wave kernels) and detect-only calls ignore it.
+ */
+#define OFS_AA_HEAD_RESIDENT 1u
+int32_t ofs_aa_detect_ex(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant, int64_t T,
+                         int32_t L, int32_t precision, void* P, void* R, void* M, uint8_t* valid,
+                         int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
+                         int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
+                         void* stream, uint32_t flags);
 
 /*
  * Which kernel ofs_aa_detect dispatches a shape to (pure query, no launch):

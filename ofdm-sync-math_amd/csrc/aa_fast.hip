@@ -128,6 +128,11 @@ __device__ __forceinline__ void st_rows2(float* span, const float (&a)[2], const
 #ifndef OFS_FAST_GATE_LATE
 #define OFS_FAST_GATE_LATE 0
 #endif
+// tuning builds: 1 = rows k < MR of the register-staged kernel keep the two P row scans (of exact zeros)
+// the kernel ran until the resident-head change; default 0 = the energy scan alone
+#ifndef OFS_FAST_HEADSCAN
+#define OFS_FAST_HEADSCAN 0
+#endif
 // DO: detect-only instantiation (P/R/M/valid not stored, events only: SURVEY §8d); S32: fp32
 // row scans (ofs_common.h row_scan; the detect-only default, issue-bound there); SV: store path of
 // the one-antenna E = 2 storing kernel = 2 * (row-paired R/M stores) + (non-temporal stores, st_out)
@@ -262,6 +267,9 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     float* Mout = DO ? nullptr : reinterpret_cast<float*>(a.M);
     const float floor_ = 1e-6f * (float)L;
     float hR[2] = {0.f, 0.f}, hM[2] = {0.f, 0.f};   // RP: R, M of the even row, held for one row
+    // resident head (OFS_AA_HEAD_RESIDENT): P[n], M[n] of n < L are +0.0 for any input (no lagged product,
+    // m = 0) and the caller's buffers already hold them, so rows k < MR store R alone (wave-uniform)
+    const bool head = !DO && a.head_resident != 0;
 
 #pragma unroll
     for (int k = 0; k < RW; ++k) {
@@ -299,7 +307,11 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
 #pragma unroll
             for (int e = E - 2; e >= 0; --e) { gS[e] = gS[e + 1] + av[e + 1]; gE[e] = gE[e + 1] + aE[e + 1]; }
             // ---- lane totals: fp64 DPP wave scan, row totals, rows inside the window ----
-            const RowScan sRr = row_scan<S32>(fS[E - 1].x), sIr = row_scan<S32>(fS[E - 1].y), sEr = row_scan<S32>(fE[E - 1]);
+            // rows k < MR have no lagged product: their lane totals, and so every part of the P scans,
+            // are +0.0 - only the energy is scanned there (the same bits: a scan of zeros gives +0.0)
+            const RowScan sEr = row_scan<S32>(fE[E - 1]);
+            RowScan sRr{0.f, 0.f, 0.0}, sIr{0.f, 0.f, 0.0};
+            if (k >= MR || OFS_FAST_HEADSCAN) { sRr = row_scan<S32>(fS[E - 1].x); sIr = row_scan<S32>(fS[E - 1].y); }
             const double totR = sRr.tot, totI = sIr.tot, totE = sEr.tot;
             const pf2 xS = pf2{sRr.x, sIr.x};                        // lanes < l
             const float xE = sEr.x;
@@ -325,6 +337,8 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
             }
 
             const int64_t o = b * a.T + nb;
+            float* const Pk = (k < MR && head) ? nullptr : Pout;   // this row's P / M stores (none: resident head)
+            float* const Mk = (k < MR && head) ? nullptr : Mout;
             // row-paired R/M stores (st_rows2): rows k0 = k & ~1 and k0 + 1 go out together from the odd
             // row when both lie entirely inside the stream and T % 4 == 0 (the span b*T + RL*k0 is then
             // 16-byte aligned and ends inside the stream); every other row stores its own float2
@@ -333,7 +347,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
 #pragma unroll
             for (int j = 0; j < V4; ++j) {
                 if (nb + 2 * j < T) {
-                    if (Pout) st_out<SP>(reinterpret_cast<float4*>(Pout + 2 * (o + 2 * j)),
+                    if (Pk) st_out<SP>(reinterpret_cast<float4*>(Pk + 2 * (o + 2 * j)),
                                          make_float4(pf[2 * j][0], pf[2 * j][1], pf[2 * j + 1][0], pf[2 * j + 1][1]));
                     // float4 R/M stores need T % 4 == 0: otherwise the last pair of a stream
                     // would spill into the next stream's first samples (and b*T+nb is not
@@ -341,11 +355,11 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                     if (paired) {                               // R/M of this row: st_rows2 below
                     } else if (E % 4 != 0 || (T & 3) != 0) {
                         if (Rout) st_out<SP>(reinterpret_cast<float2*>(Rout + o + 2 * j), make_float2(rf[2 * j], rf[2 * j + 1]));
-                        if (Mout) st_out<SP>(reinterpret_cast<float2*>(Mout + o + 2 * j), make_float2(mf[2 * j], mf[2 * j + 1]));
+                        if (Mk) st_out<SP>(reinterpret_cast<float2*>(Mk + o + 2 * j), make_float2(mf[2 * j], mf[2 * j + 1]));
                     } else if ((j & 1) == 0) {
                         if (Rout) st_out<SP>(reinterpret_cast<float4*>(Rout + o + 2 * j),
                                              make_float4(rf[2 * j], rf[2 * j + 1], rf[2 * j + 2], rf[2 * j + 3]));
-                        if (Mout) st_out<SP>(reinterpret_cast<float4*>(Mout + o + 2 * j),
+                        if (Mk) st_out<SP>(reinterpret_cast<float4*>(Mk + o + 2 * j),
                                              make_float4(mf[2 * j], mf[2 * j + 1], mf[2 * j + 2], mf[2 * j + 3]));
                     }
                     if (!DO && a.valid) { a.valid[o + 2 * j] = (k >= MR); a.valid[o + 2 * j + 1] = (k >= MR); }
@@ -358,7 +372,9 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                     } else {
                         const int64_t o0 = b * a.T + RL * (k - 1);
                         if (Rout) st_rows2<SP>(Rout + o0, hR, rf, lane);
-                        if (Mout) st_rows2<SP>(Mout + o0, hM, mf, lane);
+                        // a pair inside the head (k < MR) is not written; one that straddles L (odd MR)
+                        // goes out whole, the head row's zeros included
+                        if (Mk) st_rows2<SP>(Mk + o0, hM, mf, lane);
                     }
                 }
             }
@@ -474,7 +490,7 @@ struct AaStream {
     float2 nx[PD][NA][E];                                    // rows k..k+PD-1 in flight
     AaRowGate<E, float, false, (bool)(DO || OFS_STREAM_FF)> gate;
     float2* Pout; float* Rout; float* Mout; uint8_t* Vout;
-    bool detect;
+    bool detect, head;                                       // head: P, M of n < L resident (not stored)
     float floor_;
 
     // a row's samples of every antenna: 8-byte-aligned pair loads for whole rows, per-sample
@@ -582,20 +598,24 @@ struct AaStream {
         // ---- stores ----
         if (!DO) {
             const int64_t o = o0 + nb;
+            // resident head (OFS_AA_HEAD_RESIDENT): the FIRST rows are n < L, where P = M = +0.0 is
+            // already in the caller's buffers
+            float2* const Pk = (FIRST && head) ? nullptr : Pout;
+            float* const Mk = (FIRST && head) ? nullptr : Mout;
             if (!GUARD || k < full_rows) {
 #pragma unroll
                 for (int j = 0; j < V4; ++j) {
-                    if (Pout) *reinterpret_cast<f4u*>(Pout + o + 2 * j) = f4u{pr[2 * j], pi[2 * j], pr[2 * j + 1], pi[2 * j + 1]};
+                    if (Pk) *reinterpret_cast<f4u*>(Pk + o + 2 * j) = f4u{pr[2 * j], pi[2 * j], pr[2 * j + 1], pi[2 * j + 1]};
                     if (Rout) *reinterpret_cast<f2u*>(Rout + o + 2 * j) = f2u{rf[2 * j], rf[2 * j + 1]};
-                    if (Mout) *reinterpret_cast<f2u*>(Mout + o + 2 * j) = f2u{mf[2 * j], mf[2 * j + 1]};
+                    if (Mk) *reinterpret_cast<f2u*>(Mk + o + 2 * j) = f2u{mf[2 * j], mf[2 * j + 1]};
                 }
             } else {
 #pragma unroll
                 for (int e = 0; e < E; ++e)
                     if (nb + e < Ti) {
-                        if (Pout) Pout[o + e] = make_float2(pr[e], pi[e]);
+                        if (Pk) Pk[o + e] = make_float2(pr[e], pi[e]);
                         if (Rout) Rout[o + e] = rf[e];
-                        if (Mout) Mout[o + e] = mf[e];
+                        if (Mk) Mk[o + e] = mf[e];
                     }
             }
             if (Vout) {
@@ -660,6 +680,7 @@ __global__ OFS_STREAM_BOUNDS void aa_stream_kernel(AaFastArgs a) {
     s.Rout = DO ? nullptr : reinterpret_cast<float*>(a.R);
     s.Mout = DO ? nullptr : reinterpret_cast<float*>(a.M);
     s.Vout = DO ? nullptr : a.valid;
+    s.head = !DO && a.head_resident != 0;
     s.floor_ = 1e-6f * (float)S::L;
 
     // warm-up block (rows 0..PER-1: the first MR have no lagged product), steady blocks of

@@ -817,7 +817,7 @@ static const char* const kVariantNames[ofs::V_COUNT] = {
     "EXACT", "FAST_E", "FAST_E_DO", "FAST_SCAN", "FAST_SCAN_DO", "RTL_WPB", "PARK_DIRECT", "ZW64",
     "ZW64_GRID", "ZS", "ZF_ITEMS", "ZS_PAIR", "ZS_DEFER", "ZS_BPL", "ZS_C", "ZS_GBLK", "MC_FUSED",
     "MC_FUSE_X", "ZC_SEQ", "ZC_NODMA", "BE_FAST", "MC_PERS", "FAST_LDS", "OCC_LDS",
-    "FAST_RMPAIR", "FAST_ST_POLICY"};
+    "FAST_RMPAIR", "FAST_ST_POLICY", "FAST_HEAD"};
 // Per calling thread: a variant one thread sets steers only the calls that thread makes, so
 // concurrent callers (another thread's production calls) never see a test's forced kernel.
 struct VariantTable {
@@ -867,6 +867,16 @@ int32_t ofs_aa_detect(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant, i
                       int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
                       int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
                       void* stream) {
+    return ofs_aa_detect_ex(in_fmt, x, B, n_ant, T, L, precision, P, R, M, valid, detect, threshold, hysteresis,
+                            sample_rate, max_events, n_events, ev_int, ev_real, stream, 0u);
+}
+
+int32_t ofs_aa_detect_ex(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant, int64_t T,
+                         int32_t L, int32_t precision, void* P, void* R, void* M, uint8_t* valid,
+                         int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
+                         int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
+                         void* stream, uint32_t flags) {
+    if (flags & ~(uint32_t)OFS_AA_HEAD_RESIDENT) return OFS_EINVAL;
     if (!(fmt_ok(in_fmt) || in_fmt == OFS_CP12) || !prec_ok(precision) || OFS_MISSING(x, B * T) || B < 0 || n_ant < 1 ||
         T < 0 || L < 1)
         return OFS_EINVAL;
@@ -880,6 +890,8 @@ int32_t ofs_aa_detect(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant, i
         f.x = x; f.B = B; f.T = T; f.L = L; f.P = P; f.R = R; f.M = M; f.valid = valid;
         f.detect = detect; f.thr = threshold; f.hyst = hysteresis; f.fs = sample_rate;
         f.max_ev = max_events; f.n_ev = n_events; f.ev_i = ev_int; f.ev_r = ev_real;
+        // a permission only the fp32 fast kernels use; variant FAST_HEAD = 0: flag ignored (head rewritten)
+        f.head_resident = (flags & OFS_AA_HEAD_RESIDENT) != 0 && !ofs::variant_off(ofs::V_FAST_HEAD);
         int frc = ofs_aa_fast_try(in_fmt, precision, n_ant, f, st);
         if (frc == 1) return OFS_OK;
         if (frc < 0) return frc;

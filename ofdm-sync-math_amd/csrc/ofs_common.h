@@ -14,7 +14,7 @@ enum Variant : int {
     V_EXACT, V_FAST_E, V_FAST_E_DO, V_FAST_SCAN, V_FAST_SCAN_DO, V_RTL_WPB, V_PARK_DIRECT, V_ZW64,
     V_ZW64_GRID, V_ZS, V_ZF_ITEMS, V_ZS_PAIR, V_ZS_DEFER, V_ZS_BPL, V_ZS_C, V_ZS_GBLK, V_MC_FUSED,
     V_MC_FUSE_X, V_ZC_SEQ, V_ZC_NODMA, V_BE_FAST, V_MC_PERS, V_FAST_LDS, V_OCC_LDS,
-    V_FAST_RMPAIR, V_FAST_ST_POLICY, V_COUNT
+    V_FAST_RMPAIR, V_FAST_ST_POLICY, V_FAST_HEAD, V_COUNT
 };
 int64_t variant(Variant v);                                     // INT64_MIN when unset
 inline bool variant_is(Variant v, int64_t value) { return variant(v) == value; }
@@ -281,6 +281,9 @@ struct AaFastArgs {
     void* P; void* R; void* M; uint8_t* valid;
     int32_t detect; double thr; int32_t hyst; double fs;
     int32_t max_ev; int32_t* n_ev; int64_t* ev_i; double* ev_r;
+    // OFS_AA_HEAD_RESIDENT (runtime, wave-uniform): P[b][n], M[b][n] of n < min(L, T) already hold +0.0 and
+    // the storing aa_fast / aa_stream kernels leave them unwritten; every other kernel ignores it
+    int32_t head_resident;
 };
 // returns 1 if the fast path handled the call (launched), 0 if not applicable, <0 on error
 int ofs_aa_fast_try(int fmt, int precision, int n_ant, const AaFastArgs& a, hipStream_t st);

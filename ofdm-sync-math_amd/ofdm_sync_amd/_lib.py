@@ -21,6 +21,7 @@ _TUNING_PATH = None
 # input formats / precisions / status (include/ofdmsync.h)
 C64, C128, CI16, CP12 = 0, 1, 2, 3
 FP32, FP64 = 0, 1
+AA_HEAD_RESIDENT = 1                     # ofs_aa_detect_ex flag OFS_AA_HEAD_RESIDENT
 
 _lib = None
 
@@ -62,6 +63,9 @@ def _declare(lib):
         "ofs_status_string": (ctypes.c_char_p, [c_int32]),
         "ofs_aa_detect": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, P, P, P,
                                     P, c_int32, c_double, c_int32, c_double, c_int32, P, P, P, P]),
+        "ofs_aa_detect_ex": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, P, P, P,
+                                       P, c_int32, c_double, c_int32, c_double, c_int32, P, P, P, P,
+                                       ctypes.c_uint32]),
         "ofs_aa_plan": (c_int32, [c_int32, c_int32, c_int32, c_int64, c_int32]),
         "ofs_sc_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,
                                     c_int32, P, P, P, P]),

@@ -162,7 +162,7 @@ class AABatchDetector:
     """Preallocated, launch-only form of ``aa_detect_streaming_batched`` (serving / benchmark use).
 
     Buffers for a fixed shape [B, n_ant, T] are allocated once (``placement``: see
-    ``allocate``); ``run()`` enqueues ONE ``ofs_aa_detect`` launch on the current stream and
+    ``allocate``); ``run()`` enqueues ONE ``ofs_aa_detect_ex`` launch on the current stream and
     returns without a host synchronisation, so back-to-back calls pipeline on the GPU.  Event
     slots are ``max_events`` per stream; ``overflowed()`` (synchronising) reports whether any
     stream produced more (its count stays exact in ``n_events``; the batched function re-runs
@@ -176,13 +176,20 @@ class AABatchDetector:
     shape 1.16, 2 x 5316 1.30, 1 x 4095 1.02 (1 x 5315 0.95 is the one row-unaligned shape it helps);
     fp64 contiguous 0.99 vs 0.59 ms (cfg3), cfg2a 0.044 vs 0.030 ms.  When the driver
     cannot back a contiguous block it falls back to "plain".  ``self.placement`` is the placement used.
+
+    The result buffers are the detector's.  ``P[n]`` and ``M[n]`` of ``n < L`` are +0.0 for any
+    input (the delay line is not yet valid there), so on the fp32 fast paths (``plan()`` 1000-1199)
+    the detector zero-fills that head once, here, and ``run()`` no longer stores it
+    (``ofs_aa_detect_ex`` with ``OFS_AA_HEAD_RESIDENT``: a quarter of the headline's traffic).  A
+    caller who writes into ``result.P`` / ``result.M`` must pass ``rewrite_head=True``, which
+    stores the head on every call as before.
     """
 
     def __init__(self, B: int, T: int, n_ant: int = 1, L: int = PREAMBLE_HALF_LEN,
                  threshold: float = DETECT_THRESHOLD, hysteresis: int = DETECT_HYSTERESIS,
                  sample_rate: float = SAMPLE_RATE_HZ, *, precision="fp32", in_dtype=None,
                  outputs=("P", "R", "M"), detect: bool = True, max_events: int = 4,
-                 placement: str = "auto", device=None):
+                 placement: str = "auto", rewrite_head: bool = False, device=None):
         if placement not in AA_PLACEMENTS:
             raise ValueError(f"placement must be one of {AA_PLACEMENTS}, got {placement!r}")
         dev = torch.device(device) if device is not None else _lib.require_gpu()
@@ -218,9 +225,17 @@ class AABatchDetector:
         self.result = AABatchResult(P, R, M, V, n_ev, ev_i, ev_r)
         self.B, self.T, self.n_ant, self.L, self.prec, self.max_events = B, T, n_ant, int(L), prec, E
         self.placement, self.device = placement, dev
-        self._fn = _lib.lib().ofs_aa_detect
+        self._fn = _lib.lib().ofs_aa_detect_ex
         self._tail = (prec, _lib.ptr(P), _lib.ptr(R), _lib.ptr(M), _lib.ptr(V), int(detect), float(threshold),
                       int(hysteresis), float(sample_rate), E, _lib.ptr(n_ev), _lib.ptr(ev_i), _lib.ptr(ev_r))
+        # resident head: the constant zeros of P, M at n < L go in once, run() leaves them alone
+        self.head_resident = (not rewrite_head and B > 0 and T > 0 and 1000 <= self.plan() < 1200
+                              and (P is not None or M is not None))
+        if self.head_resident:
+            for o in (P, M):
+                if o is not None:
+                    o[:, :min(int(L), T)].zero_()
+        self._flags = _lib.AA_HEAD_RESIDENT if self.head_resident else 0
 
     def plan(self) -> int:
         """ofs_aa_plan of this shape (which kernel ``run`` launches)."""
@@ -232,8 +247,8 @@ class AABatchDetector:
         if x.device != self.device or not x.is_contiguous() or x.numel() != self.x.numel() or x.dtype != self.x.dtype:
             raise ValueError("x must be a contiguous device tensor shaped and typed like AABatchDetector.x")
         rc = self._fn(self.fmt, x.data_ptr(), self.B, self.n_ant, self.T, self.L, *self._tail,
-                      _lib.stream_ptr() if stream is None else stream)
-        _lib.check(rc, "ofs_aa_detect")
+                      _lib.stream_ptr() if stream is None else stream, self._flags)
+        _lib.check(rc, "ofs_aa_detect_ex")
         return self.result
 
     def overflowed(self) -> bool:

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--detect-only", action="store_true")
+    ap.add_argument("--head-resident", action="store_true",
+                    help="aa: P/M heads zeroed once, calls through ofs_aa_detect_ex with OFS_AA_HEAD_RESIDENT")
     ap.add_argument("--no-check", action="store_true", help="variants may differ in rounding (no bit-equality check)")
     ap.add_argument("--op", choices=("aa", "scminn", "sc", "comb", "minn", "zcfreq"), default="aa",
                     help="aa: ofs_aa_detect; scminn: ofs_sc_minn_metric (cfg4 fused S&C + Minn, N = 2 L); zcfreq: "
@@ -47,6 +49,9 @@ def main():
     P = None if a.detect_only else torch.empty((B, T), dtype=torch.complex64, device=dev)
     R = None if a.detect_only else torch.empty((B, T), dtype=torch.float32, device=dev)
     M = None if a.detect_only else torch.empty((B, T), dtype=torch.float32, device=dev)
+    if a.head_resident and not a.detect_only:
+        P[:, :min(L, T)].zero_()
+        M[:, :min(L, T)].zero_()
     n_ev = torch.zeros(B, dtype=torch.int32, device=dev)
     ev_i = torch.empty((B, E, 4), dtype=torch.int64, device=dev)
     ev_r = torch.empty((B, E, 4), dtype=torch.float64, device=dev)
@@ -58,18 +63,20 @@ def main():
         libs.append((os.path.basename(p), l))
     args = (_lib.C64, x.data_ptr(), B, na, T, L, _lib.FP32, _lib.ptr(P), _lib.ptr(R), _lib.ptr(M), None, 1,
             0.15, 128, 15.36e6, E, n_ev.data_ptr(), ev_i.data_ptr(), ev_r.data_ptr(), st.cuda_stream)
+    run = (lambda l: l.ofs_aa_detect_ex(*args, _lib.AA_HEAD_RESIDENT)) if a.head_resident else (
+        lambda l: l.ofs_aa_detect(*args))
     times = {n: [] for n, _ in libs}
     ref = None
     for r in range(a.rounds):
         order = libs[r % len(libs):] + libs[:r % len(libs)]
         for name, l in order:
             for _ in range(3):
-                assert l.ofs_aa_detect(*args) == 0
+                assert run(l) == 0
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(st)
             for _ in range(a.steps):
-                l.ofs_aa_detect(*args)
+                run(l)
             e1.record(st)
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / a.steps)
@@ -83,7 +90,7 @@ def main():
     for name, _ in libs:
         ms = statistics.median(times[name])
         print(json.dumps(dict(lib=name, shape=[B, na, T, L], plan=libs[0][1].ofs_aa_plan(_lib.C64, _lib.FP32, na, T, L),
-                              ms_median=round(ms, 4), ms_all=[round(t, 4) for t in times[name]],
+                              head_resident=a.head_resident, ms_median=round(ms, 4), ms_all=[round(t, 4) for t in times[name]],
                               frac=round(alg / (ms / 1e3) / 8e12, 4))), flush=True)
 
 
