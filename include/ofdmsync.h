@@ -168,6 +168,57 @@ int32_t ofs_aa_detect_ex(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant
 int32_t ofs_aa_plan(int32_t in_fmt, int32_t precision, int32_t n_ant, int64_t T, int32_t L);
 
 /*
+ * Resumable chunked [A][A] detection for integer streams of any length (no reference counterpart:
+ * the reference's sample-by-sample loop, sync_aa.py:421-571, is the specification).
+ *
+ * A stream is fed in consecutive chunks of Tc samples; ofs_aa_detect_chunk returns the chunk's
+ * P/R/M/valid and the gate events that CLOSED among its samples, and keeps what the next call needs
+ * in a caller-owned state buffer on the device.  The library allocates nothing and keeps no global
+ * state.
+ *   in_fmt  OFS_CI16: x = [B][n_ant][Tc] int16 (I, Q);  OFS_CP12: x = [B][Tc][3 * n_ant] bytes.
+ *           Arithmetic is fp64 (as OFS_FP64 in ofs_aa_detect).  n_ant 1-2; L 64, 128, 256, 512 or 1024.
+ *   state   [B][ofs_aa_chunk_state_bytes(n_ant, L)] bytes, 16-byte aligned, device memory.  The layout
+ *           is opaque; ALL-ZERO BYTES ARE A FRESH STREAM, so any subset of streams is reset with a
+ *           memset of its rows (stream-ordered with the calls).  One state row belongs to one stream:
+ *           in_fmt, n_ant, L, threshold, hysteresis and detect must not change between the calls of
+ *           a stream (sample_rate and max_events may), and the calls of a stream must be ordered
+ *           (same HIP stream, or synchronised by the caller).
+ *   P, R, M, valid  [B][Tc] c128 / f64 / f64 / uint8, each nullable; index i of a call is the stream's
+ *           absolute sample n = (samples of earlier calls) + i; valid = n >= L.
+ *   events  as ofs_aa_detect, written from slot 0 of every call, with ABSOLUTE int64 indices
+ *           (peak_index, gate_start, gate_end, frame_start = peak_index - 2L + 1).  n_events[b] is the
+ *           number of gates that closed during this call (exact even above max_events).  A gate still
+ *           open at the end of the chunk is carried, not closed, unless final != 0: then it closes
+ *           at gate_end = the stream's sample count, as ofs_aa_detect closes it at T, and the state
+ *           is a fresh stream again after the call.
+ *   Tc      1 .. ofs_aa_chunk_max_samples(n_ant, L) = 2^21 / n_ant - 2L ((Tc + 2L) * n_ant <= 2^21
+ *           keeps every window sum an exact integer below 2^53); Tc = 0 with final != 0 is a flush:
+ *           no samples, open gates close and emit (x, P, R, M, valid unused).
+ * EQUIVALENCE GUARANTEE.  For any split of a stream into chunks within the per-call limit, the
+ * concatenated P, R, M, valid and the sequence of events (the last call final) equal bit for bit
+ * what ONE ofs_aa_detect call on the whole stream returns on its integer-exact plan
+ * (ofs_aa_plan 2000-2999); for streams longer than that plan reaches they equal the reference's
+ * float64 loop on P, R, valid and the events' integers, with M and the events' reals as close as
+ * ofs_aa_detect's (the window sums are the same exact integers).
+ * Calls are stream-ordered and never synchronise with the host: consecutive chunks may be enqueued
+ * back to back.  OFS_EINVAL (before any launch): another in_fmt, n_ant outside 1-2, an L outside the
+ * table, Tc < 0 or above the limit, Tc = 0 without final, B < 0, a null or misaligned state with
+ * B > 0, a null x with B * Tc > 0, hysteresis > OFS_AA_CHUNK_MAX_HYSTERESIS, detect with a null
+ * n_events or with null event arrays while max_events > 0.  There is no fall-back to the general
+ * engine.  ofs_aa_chunk_state_bytes returns the bytes of ONE stream's state (a multiple of 16) and
+ * ofs_aa_chunk_max_samples the largest Tc of one call; both return OFS_EINVAL (< 0) for an unsupported
+ * n_ant or L.
+ */
+#define OFS_AA_CHUNK_MAX_HYSTERESIS (1 << 28)
+int64_t ofs_aa_chunk_state_bytes(int32_t n_ant, int32_t L);
+int64_t ofs_aa_chunk_max_samples(int32_t n_ant, int32_t L);
+int32_t ofs_aa_detect_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_ant, int64_t Tc, int32_t L,
+                            void* state, void* P, void* R, void* M, uint8_t* valid,
+                            int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
+                            int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
+                            int32_t final, void* stream);
+
+/*
  * Schmidl-Cox half-symbol metric, reference index convention d = 0 .. T-N.
  * r_mode 0 replaces sc.sc_streaming_metric (sc.py:42-78; R = second-half energy);
  * r_mode 1 replaces combined_sc_min.schmidl_cox_streaming_metric (combined_sc_min.py:116-164;

@@ -50,9 +50,19 @@ namespace ofs {
 constexpr int GATE_NOKEY = 1 << 20;      // row-relative keys
 constexpr int ABS_NOKEY = 0x7fffffff;    // absolute sample indices
 
-template <int E, class V, bool RTL = false, bool FF = true, bool DEFER = true>
-struct AaRowGate {
+// ABS (resumable streams, aa_chunk.hip): one call sees a piece of a longer stream.  Its positions
+// are call-local "gate coordinates"; the absolute sample index is the gate coordinate + abs0.  load()
+// takes the machine's wave-uniform fields from the previous call (absolute indices), save() gives
+// them back, and emit() writes absolute indices.  The start and the peak of a gate that was already
+// open at load() may lie any distance back, so they stay absolute (ev0_abs, b0_abs) behind the
+// CARRIED mark.  The other forms never touch these members.
+template <bool ABS> struct AaGateAbs {};                   // the other forms carry no extra member
+template <> struct AaGateAbs<true> { int64_t abs0, ev0_abs, b0_abs; };
+
+template <int E, class V, bool RTL = false, bool FF = true, bool DEFER = true, bool ABS = false>
+struct AaRowGate : AaGateAbs<ABS> {
     static constexpr int RL = 64 * E;
+    static constexpr int CARRIED = INT32_MIN;
     int Hp, L, max_ev, toff;
     double thr, fs;
     int64_t* evi;
@@ -84,7 +94,7 @@ struct AaRowGate {
                 if (lane < 4) ei[lane] = f[lane & 3];
             } else {
                 double* er = evr + (int64_t)n_ev * 4;
-                const int64_t f[4] = {bidx, ev_start, gate_end, (int64_t)bidx - 2 * L + 1};
+                const int64_t f[4] = {out_peak(), out_start(), out_pos(gate_end), out_peak() - 2 * L + 1};
                 if (lane < 4) {
                     ei[lane] = f[lane & 3];
                 } else {
@@ -313,6 +323,46 @@ struct AaRowGate {
             if (gate_open) { if (DEFER && OFS_GATE_DEFER) merge(); emit(lane, T); }
             if (lane == 0) *n_ev_out = n_ev;
         }
+    }
+
+    // ---- event indices as written (ABS: absolute) ----
+    __device__ __forceinline__ int64_t out_pos(int g) const {
+        if constexpr (ABS) return (int64_t)g + this->abs0;
+        else return g;
+    }
+    __device__ __forceinline__ int64_t out_peak() const {
+        if constexpr (ABS) return bidx == CARRIED ? this->b0_abs : out_pos(bidx);
+        else return bidx;
+    }
+    __device__ __forceinline__ int64_t out_start() const {
+        if constexpr (ABS) return ev_start == CARRIED ? this->ev0_abs : out_pos(ev_start);
+        else return ev_start;
+    }
+
+    // ---- ABS: resumable streams ----
+
+    // after init(): the state an earlier call saved.  carry_p1 = 1 + absolute index of the last
+    // above-threshold sample, 0 = none; one further back than gate coordinate 0 is more than
+    // max(H, 1) before this call's first sample (the caller's choice of abs0) and is "none": its
+    // gate has closed and any above sample opens the next.
+    __device__ __forceinline__ void load(int64_t abs0_, int64_t carry_p1, int open, int64_t ev_start_abs,
+                                         int64_t bidx_abs, V bpm_, V bpr_, V bpi_, V bm_) {
+        static_assert(ABS && !RTL, "resumable form of the sync_aa machine");
+        this->abs0 = abs0_; this->ev0_abs = ev_start_abs; this->b0_abs = bidx_abs;
+        const int64_t cg = carry_p1 - 1 - abs0_;
+        carry_last = (carry_p1 > 0 && cg >= 0) ? (int)cg : -1;
+        if (open) {
+            gate_open = 1; ev_start = CARRIED; bidx = CARRIED;
+            bpm = bpm_; bpr = bpr_; bpi = bpi_; bm = bm_;
+        }
+    }
+    // after the call's last row (and merge() if a gate is open): the fields for the next call
+    __device__ __forceinline__ void save(int64_t& carry_p1, int& open, int64_t& ev_start_abs, int64_t& bidx_abs) const {
+        static_assert(ABS && !RTL, "resumable form of the sync_aa machine");
+        carry_p1 = carry_last >= 0 ? out_pos(carry_last) + 1 : 0;
+        open = gate_open;
+        ev_start_abs = out_start();
+        bidx_abs = out_peak();
     }
 };
 

@@ -67,6 +67,11 @@ def _declare(lib):
                                        P, c_int32, c_double, c_int32, c_double, c_int32, P, P, P, P,
                                        ctypes.c_uint32]),
         "ofs_aa_plan": (c_int32, [c_int32, c_int32, c_int32, c_int64, c_int32]),
+        "ofs_aa_chunk_state_bytes": (c_int64, [c_int32, c_int32]),
+        "ofs_aa_chunk_max_samples": (c_int64, [c_int32, c_int32]),
+        "ofs_aa_detect_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, P, P, P, P, P,
+                                          c_int32, c_double, c_int32, c_double, c_int32, P, P, P,
+                                          c_int32, P]),
         "ofs_sc_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,
                                     c_int32, P, P, P, P]),
         "ofs_minn_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,
