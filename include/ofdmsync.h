@@ -98,7 +98,8 @@ const char* ofs_status_string(int32_t status);
  *   ZC_NODMA     1: zc_v2 CFAR tiles through registers instead of LDS-DMA
  *   BE_FAST      0: receiver back-end through the generic kernel
  *   FAST_LDS     n > 0: bytes of unused dynamic LDS per workgroup of the aa_fast kernel (occupancy
- *                cap; default 16384 for the one-antenna storing kernel = 10 per CU, 1 = no cap)
+ *                cap; default 16384 for the one-antenna storing kernel = 10 per CU, 23000 = 7 per CU for
+ *                its full-stream form, 1 = no cap)
  *   OCC_LDS      n >= 0: bytes of unused dynamic LDS added to the other wave-per-stream launches
  *                (aa_stream, win_fast, aa_exact, rtl_exact, the fast back-end; occupancy A/B)
  *   FAST_RMPAIR  0|1: R and M of two adjacent rows of the one-antenna E = 2 storing aa_fast kernel as
@@ -106,6 +107,9 @@ const char* ofs_status_string(int32_t status);
  *   FAST_ST_POLICY 0|1: that kernel's P/R/M stores plain / non-temporal (default 1)
  *   FAST_HEAD    0: ofs_aa_detect_ex ignores OFS_AA_HEAD_RESIDENT (the P/M head is rewritten; A/B of
  *                both arms on the same buffers)
+ *   FAST_FULL    0: the headline shape (one antenna, T = 1024, L = 128 | 256 | 512, P, R, M and events,
+ *                no valid) through the generic aa_fast kernel instead of its full-stream form (same
+ *                bits; A/B and the tests' reference arm)
  * ofs_debug_set_variant returns OFS_EINVAL for an unknown name; value OFS_VARIANT_UNSET clears
  * one variant, ofs_debug_reset_variants clears all.  The table is per calling thread
  * (thread_local): a variant set by one thread steers only the calls that same thread makes, and

@@ -18,6 +18,8 @@
 // Gate / peak / CFO events (sync_aa.py:495-568) use the closed form of aa_events
 // (ofdmsync.hip), streamed row by row (aa_gate.h): prev-above by lane-serial + DPP max-scan,
 // opens/closes by ballot, per-gate argmax by wave reductions, scalar carry between rows.
+#include <cfloat>
+#include <cmath>
 #include "ofs_common.h"
 #include "aa_gate.h"
 #include "ofdmsync.h"
@@ -42,6 +44,8 @@ constexpr int FAST_WG = OFS_FAST_WG;   // one wave = one stream per workgroup (p
 #endif
 constexpr int TMAX = 1024;        // stream length handled by the fast path
 constexpr int FAST_CAP_LDS = 160 * 1024 / 10;   // occupancy cap of the storing kernel: 10 workgroups per CU (launch)
+// its full-stream form: 7 per CU (the measured value; at most 160 KiB / 7 = 23405, less the allocation granule)
+constexpr int FAST_CAP_LDS_FULL = 23000;
 
 // cache policy knob (tuning builds): LDS-DMA aux bits
 #ifndef OFS_DMA_AUX
@@ -136,9 +140,20 @@ __device__ __forceinline__ void st_rows2(float* span, const float (&a)[2], const
 // DO: detect-only instantiation (P/R/M/valid not stored, events only: SURVEY §8d); S32: fp32
 // row scans (ofs_common.h row_scan; the detect-only default, issue-bound there); SV: store path of
 // the one-antenna E = 2 storing kernel = 2 * (row-paired R/M stores) + (non-temporal stores, st_out)
-template <int E, int MR, int NA, bool DO, bool S32, int SV = 0>
+//
+// FS: full-stream form of the SV = 3 kernel (launch(): T == TMAX, P, R, M and the event outputs all
+// present, no valid, detect on; variant FAST_FULL = 0 keeps the generic form).  Same arithmetic and data
+// movement, same bits; what goes is the generality around them: T is a constant (no row guards, no
+// zero-fill selects, no clamped load index, every R/M row pair goes out paired), no pointer is tested,
+// each buffer is one scalar base per stream plus one 32-bit lane offset (16 * lane bytes for x, P and
+// the paired R/M spans alike; the row offset is a constant), the above flags are an fp32 compare against
+// AaFastArgs::thr32, and the gate machine is chosen at launch: FS = 1 the scan-free rows (max(hyst, 1)
+// >= RL), FS = 2 the scan rows - not both bodies inline behind a per-row test.
+template <int E, int MR, int NA, bool DO, bool S32, int SV = 0, int FS = 0>
 __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     static_assert(SV == 0 || (E == 2 && NA == 1 && !DO), "store-path variants: one-antenna E = 2 storing kernel");
+    static_assert(FS == 0 || (SV == 3 && !S32 && OFS_FAST_STAGE == 1 && !OFS_FAST_GATE_LATE), "full-stream form: the headline's kernel");
+    constexpr bool FULL = FS != 0;
     constexpr int SP = SV & 1;                 // output store cache policy
     constexpr bool RP = (SV & 2) != 0;         // R/M of rows k, k+1 (k even) as one 16-byte store per lane
     constexpr int RL = 64 * E;                 // samples per row
@@ -150,14 +165,17 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     __shared__ float4 lds[FAST_WG / 64][NA * RW * V4][64];
 #endif
     const int lane = threadIdx.x & 63;
-    const int w = threadIdx.x >> 6;
+    // (FULL: one wave per workgroup is wave 0, which keeps the stream index and every base scalar)
+    const int w = (FULL && FAST_WG == 64) ? 0 : threadIdx.x >> 6;
     // block order: one antenna plain blockIdx, two the XCD remap (paired under the occupancy cap,
     // profiles/r06n_headline_remap_ff_ab.txt: without the remap cfg3 0.2994 -> 0.2940 ms, detect-only
     // 0.1036 -> 0.0949, T 4096 1.225 -> 1.211; two antennas 0.4004 -> 0.4055 and the 2 x 5315 shape
     // slower in 2 of 3 rounds - they keep it)
     const int64_t b = (int64_t)(NA == 1 ? blockIdx.x : xcd_block()) * (FAST_WG / 64) + w;
     if (b >= a.B) return;
-    const int T = (int)a.T;
+    const int T = FULL ? TMAX : (int)a.T;
+    // FULL: byte offset of this lane's 16 bytes in a row of x / P and in a row pair of R / M
+    const uint32_t lo16 = 16u * (uint32_t)lane;
 #if OFS_FAST_STAGE == 0
     // row-major DMA order (row k of every antenna before row k+1): row k has landed once at most
     // the later rows' DMAs and the output stores of rows < k (SPR per row, all younger) are
@@ -221,6 +239,11 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     // register staging: every row of the lane's samples is loaded up front (RW * V4 float4), each
     // row's first use waits only for its own loads (vmcnt counts in order)
     float4 xreg[NA][RW][V4];
+    if constexpr (FULL) {
+        const char* const xb = reinterpret_cast<const char*>(a.x) + b * (TMAX * 8);
+#pragma unroll
+        for (int k = 0; k < RW; ++k) xreg[0][k][0] = *reinterpret_cast<const float4*>(xb + RL * 8 * k + lo16);
+    } else {
 #pragma unroll
     for (int t = 0; t < NA; ++t) {
         const float2* xs = reinterpret_cast<const float2*>(a.x) + (b * NA + t) * a.T;
@@ -233,13 +256,14 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                 xreg[t][k][j] = *reinterpret_cast<const float4*>(xs + n);
             }
     }
+    }
     auto ldrow = [&](int t, int k, int j) { return xreg[t][k][j]; };
     auto row_wait = [&](int) {};
 #endif
     auto xrow = [&](int t, int k, pf2 (&c)[E]) {
 #pragma unroll
         for (int j = 0; j < V4; ++j) {
-            const bool ok = RL * k + E * lane + 2 * j < T;
+            const bool ok = FULL || RL * k + E * lane + 2 * j < T;
             const float4 v = ldrow(t, k, j);
             c[2 * j] = ok ? pf2{v.x, v.y} : pf2{0.f, 0.f};
             c[2 * j + 1] = ok ? pf2{v.z, v.w} : pf2{0.f, 0.f};
@@ -258,7 +282,8 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     constexpr int GR = RW - MR > 0 ? RW - MR : 1;             // gated rows (k >= MR)
     __shared__ float4 gl[FAST_WG / 64][GR][E][64];            // (M, |P|^2, Re P, Im P) per sample
 #endif
-    if (a.detect)
+    const bool detect = FULL || a.detect;
+    if (detect)
         gate.init(a.hyst, L, a.thr, a.fs, a.max_ev, a.ev_i + b * (int64_t)a.max_ev * 4,
                   a.ev_r + b * (int64_t)a.max_ev * 4);
 
@@ -270,10 +295,14 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     // resident head (OFS_AA_HEAD_RESIDENT): P[n], M[n] of n < L are +0.0 for any input (no lagged product,
     // m = 0) and the caller's buffers already hold them, so rows k < MR store R alone (wave-uniform)
     const bool head = !DO && a.head_resident != 0;
+    // FULL: this stream's outputs, one scalar base each
+    char* const Pb = FULL ? reinterpret_cast<char*>(a.P) + b * (TMAX * 8) : nullptr;
+    float* const Rb = FULL ? reinterpret_cast<float*>(a.R) + b * TMAX : nullptr;
+    float* const Mb = FULL ? reinterpret_cast<float*>(a.M) + b * TMAX : nullptr;
 
 #pragma unroll
     for (int k = 0; k < RW; ++k) {
-        if (RL * k < T) {                                       // wave-uniform row guard
+        if (FULL || RL * k < T) {                               // wave-uniform row guard
             const int nb = RL * k + E * lane;                   // first sample of this lane
             // ---- lagged products x[n]·conj(x[n-L]) and energies, fp32 ----
             // summed over the antennas, like the reference's per-antenna running sums added up
@@ -336,6 +365,17 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                 pf[e][0] = P.x; pf[e][1] = P.y; rf[e] = RR; mf[e] = m; pmf[e] = pm;
             }
 
+            if constexpr (FULL) {
+                // every row whole, every pair paired; rows k < MR of a resident head store R alone
+                const bool pm_row = !(k < MR && head);
+                if (pm_row) st_out<SP>(reinterpret_cast<float4*>(Pb + RL * 8 * k + lo16), make_float4(pf[0][0], pf[0][1], pf[1][0], pf[1][1]));
+                if ((k & 1) == 0) {
+                    hR[0] = rf[0]; hR[1] = rf[1]; hM[0] = mf[0]; hM[1] = mf[1];
+                } else {
+                    st_rows2<SP>(Rb + RL * (k - 1), hR, rf, lane);
+                    if (pm_row) st_rows2<SP>(Mb + RL * (k - 1), hM, mf, lane);
+                }
+            } else {
             const int64_t o = b * a.T + nb;
             float* const Pk = (k < MR && head) ? nullptr : Pout;   // this row's P / M stores (none: resident head)
             float* const Mk = (k < MR && head) ? nullptr : Mout;
@@ -378,9 +418,10 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                     }
                 }
             }
+            }
 
             // ---- events: closed-form gate machine, streamed per row (aa_gate.h) ----
-            if (a.detect && k >= MR) {
+            if (detect && k >= MR) {
 #if OFS_FAST_GATE_LATE
 #pragma unroll
                 for (int e = 0; e < E; ++e) gl[w][k >= MR ? k - MR : 0][e][lane] = make_float4(mf[e], pmf[e], pf[e][0], pf[e][1]);
@@ -388,7 +429,15 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                 float pr[E], pi[E];
 #pragma unroll
                 for (int e = 0; e < E; ++e) { pr[e] = pf[e][0]; pi[e] = pf[e][1]; }
-                gate.row(lane, k, nb, T, mf, pmf, pr, pi);
+                if constexpr (FULL) {
+                    // m >= thr32 in fp32 is (double)m >= thr for every m and thr (launch())
+                    bool ab[E];
+#pragma unroll
+                    for (int e = 0; e < E; ++e) ab[e] = mf[e] >= a.thr32;
+                    gate.template row_flags<FS, true>(lane, k, nb, T, ab, pmf, pr, pi, mf);
+                } else {
+                    gate.row(lane, k, nb, T, mf, pmf, pr, pi);
+                }
 #endif
             }
         }
@@ -412,7 +461,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
         }
     }
 #endif
-    if (a.detect) gate.finish(lane, T, a.n_ev + b);
+    if (detect) gate.finish(lane, T, a.n_ev + b);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -735,6 +784,20 @@ bool scan32(bool det_only) {
     return det_only;
 }
 
+// The smallest float >= thr.  For a float m, (double)m >= thr exactly when m >= that float: a float at
+// or above thr is at or above the smallest such float, and that float is itself >= thr.  NaN stays NaN
+// (both compares false), thr beyond FLT_MAX gives +inf (only m = +inf passes, as in fp64), thr below
+// -FLT_MAX gives -FLT_MAX (m = -inf fails, as in fp64), a subnormal stays exact (the kernels keep fp32
+// subnormals); the sign of a zero does not matter to >=.
+float thr_as_f32(double thr) {
+    if (thr != thr || thr == (double)INFINITY || thr == -(double)INFINITY) return (float)thr;
+    if (thr > (double)FLT_MAX) return INFINITY;
+    if (thr < -(double)FLT_MAX) return -FLT_MAX;
+    float f = (float)thr;                                    // in range: round to nearest
+    if ((double)f < thr) f = nextafterf(f, INFINITY);
+    return f;
+}
+
 template <int E, int MR, int NA>
 int launch(const AaFastArgs& a, hipStream_t st) {
     const bool det_only = a.detect && !a.P && !a.R && !a.M && !a.valid;
@@ -757,6 +820,31 @@ int launch(const AaFastArgs& a, hipStream_t st) {
     if constexpr (E == 2 && NA == 1) {
         if (!det_only && !s32) {
             const int sv = (ofs::variant_or(ofs::V_FAST_RMPAIR, 1) != 0 ? 2 : 0) | (ofs::variant_or(ofs::V_FAST_ST_POLICY, 1) == 1 ? 1 : 0);
+            // full-stream form (aa_fast_kernel, FS) for the shape the batch detector launches: a whole
+            // stream, every output and the events; windows of 1, 2, 4 rows.  Variant FAST_FULL = 0: the
+            // generic form (A/B, the tests' reference arm).  The gate rows are chosen here, once.
+            if constexpr (MR == 1 || MR == 2 || MR == 4) {
+                if (sv == 3 && a.T == TMAX && a.P && a.R && a.M && !a.valid && a.detect && a.n_ev && a.ev_i && a.ev_r &&
+                    !ofs::variant_off(ofs::V_FAST_FULL)) {
+                    AaFastArgs f = a;
+                    f.thr32 = thr_as_f32(a.thr);
+                    // Its own occupancy cap: with a third fewer instructions per stream the waves reach their
+                    // loads and stores sooner, and the steady-state optimum moves from 10 to 7 workgroups per CU
+                    // (paired on the same buffers, 8 allocations in 3 sessions, profiles/headline_full_cap_*.jsonl:
+                    // 7 per CU -4.1..-8.6 % against 10, 8 and 9 per CU -0.9..-3.0 %, 6 per CU +7.4..+9.9 %; the
+                    // generic form at 7 per CU +17..+20 %).  At 10 per CU this form is 2.6 % faster to 8.2 %
+                    // slower than the generic one in steady state; at 7 it is 0.4..6.8 % faster.  The first
+                    // launches after other work (bench.py's 110) prefer 10 by ~4 % (0.198-0.209 against
+                    // 0.205-0.213 ms) - both beat the generic form's 0.220-0.226 ms.  DESIGN.md §4.1.
+                    const int64_t padf = ofs::variant_or(ofs::V_FAST_LDS, FAST_CAP_LDS_FULL);
+                    const size_t shmf = padf > 0 && padf <= 65536 ? (size_t)padf : 0;
+                    if ((a.hyst > 1 ? a.hyst : 1) >= 64 * E)
+                        hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 1>), grid, blk, shmf, st, f);
+                    else
+                        hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 2>), grid, blk, shmf, st, f);
+                    return hipGetLastError() == hipSuccess ? 1 : OFS_EHIP;
+                }
+            }
             switch (sv) {
                 case 0: hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 0>), grid, blk, shm, st, a); break;
                 case 1: hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 1>), grid, blk, shm, st, a); break;

@@ -138,6 +138,7 @@ struct AaRowGate : AaGateAbs<ABS> {
         lv = (V)-1; lpr = (V)0; lpi = (V)0; lm = (V)0;
         lk = RTL ? -1 : ABS_NOKEY;
     }
+    template <bool FULLROW = false>
     __device__ __forceinline__ void accumulate(int lane, int k, int nb, int T, int lo, int hi, const V (&pm)[E],
                                                const V (&pr)[E], const V (&pi)[E], const V (&m)[E]) {
 #if OFS_GATE_NOACC == 1             // diagnostic builds only (wrong peaks): no per-lane peak tracking
@@ -146,7 +147,7 @@ struct AaRowGate : AaGateAbs<ABS> {
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int key = E * lane + e;
-            const bool in = nb + e < T && key >= lo && key <= hi;
+            const bool in = (FULLROW || nb + e < T) && key >= lo && key <= hi;
             const bool better = RTL ? (pm[e] >= lv) : (pm[e] > lv);
 #if OFS_GATE_NOACC == 2             // diagnostic builds only (wrong payload): value + index tracked
             if (in && better) { lv = pm[e]; lk = RL * k + key; }
@@ -177,16 +178,22 @@ struct AaRowGate : AaGateAbs<ABS> {
         lane_reset();
     }
     // a gate's samples within one row; OFS_GATE_DEFER = 0 reduces over the wave every row
+    template <bool FULLROW = false>
     __device__ __forceinline__ void seg(int lane, int k, int nb, int T, int lo, int hi, const V (&pm)[E],
                                         const V (&pr)[E], const V (&pi)[E], const V (&m)[E]) {
-        accumulate(lane, k, nb, T, lo, hi, pm, pr, pi, m);
+        accumulate<FULLROW>(lane, k, nb, T, lo, hi, pm, pr, pi, m);
         if (!(DEFER && OFS_GATE_DEFER)) merge();
     }
     __device__ __forceinline__ void open_at(int start) {
         gate_open = 1; ev_start = start; bpm = (V)-1; lane_reset();
     }
 
-    // generic row: above flags given; pm = the value whose arg-extremum is the peak
+    // generic row: above flags given; pm = the value whose arg-extremum is the peak.
+    // MODE: 0 = the scan-free rows or the scan rows by a per-row test of Hp >= RL (both inline); the
+    // caller that has made that choice for the whole stream passes 1 (scan-free: Hp >= RL holds) or 2
+    // (scan rows) and gets that body alone.  FULLROW: every sample of the row lies inside the stream
+    // (RL * (k + 1) <= T) and ab[] needs no n < T mask, so the per-sample tests against T are dropped.
+    template <int MODE = 0, bool FULLROW = false>
     __device__ __forceinline__ void row_flags(int lane, int k, int nb, int T, const bool (&ab)[E],
                                               const V (&pm)[E], const V (&pr)[E], const V (&pi)[E],
                                               const V (&m)[E]) {
@@ -224,7 +231,7 @@ struct AaRowGate : AaGateAbs<ABS> {
             return;
         }
 #endif
-        if (FF && OFS_GATE_FASTFLAGS && (OFS_GATE_FFONLY || Hp >= RL)) {
+        if (MODE == 1 || (MODE == 0 && FF && OFS_GATE_FASTFLAGS && (OFS_GATE_FFONLY || Hp >= RL))) {
             // hysteresis at least one row: only the row's FIRST above sample can open a gate and
             // only carry_last + Hp can close one (before that first sample), so the machine runs
             // on the above ballots alone, in scalar registers - no prefix scan
@@ -241,8 +248,8 @@ struct AaRowGate : AaGateAbs<ABS> {
             int seg_lo = gate_open ? 0 : -1;
             if (carry_last >= 0) {                                   // close at carry_last + Hp
                 const int c = carry_last + Hp;
-                if (c >= base && c < base + RL && c < T && c - base < first) {
-                    seg(lane, k, nb, T, seg_lo, c - base, pm, pr, pi, m);
+                if (c >= base && c < base + RL && (FULLROW || c < T) && c - base < first) {
+                    seg<FULLROW>(lane, k, nb, T, seg_lo, c - base, pm, pr, pi, m);
                     if (DEFER && OFS_GATE_DEFER) merge();
                     emit(lane, c);
                     gate_open = 0; seg_lo = -1;
@@ -255,7 +262,7 @@ struct AaRowGate : AaGateAbs<ABS> {
                 }
                 carry_last = base + last;
             }
-            if (gate_open) seg(lane, k, nb, T, seg_lo, RL - 1, pm, pr, pi, m);
+            if (gate_open) seg<FULLROW>(lane, k, nb, T, seg_lo, RL - 1, pm, pr, pi, m);
             return;
         }
 #if OFS_GATE_FFONLY                 // diagnostic builds only (H >= one row assumed): no scan path
@@ -274,7 +281,7 @@ struct AaRowGate : AaGateAbs<ABS> {
             const int n = nb + e;
             const int pe = run;
             if (ab[e]) run = n;
-            const bool cl = (n < T) && run >= 0 && (n - run) == Hp;
+            const bool cl = (FULLROW || n < T) && run >= 0 && (n - run) == Hp;
             const bool op = ab[e] && (pe < 0 || (n - 1 - pe) >= Hp);
             Om[e] = __ballot(op);
             Cm[e] = __ballot(cl);
@@ -300,7 +307,7 @@ struct AaRowGate : AaGateAbs<ABS> {
                 if (is_open) {
                     open_at(RL * k + key); seg_lo = key;
                 } else {
-                    seg(lane, k, nb, T, seg_lo, key, pm, pr, pi, m);
+                    seg<FULLROW>(lane, k, nb, T, seg_lo, key, pm, pr, pi, m);
                     if (DEFER && OFS_GATE_DEFER) merge();
                     emit(lane, RL * k + key);
                     gate_open = 0; seg_lo = -1;
@@ -308,7 +315,7 @@ struct AaRowGate : AaGateAbs<ABS> {
                 pos = key;
             }
         }
-        if (gate_open) seg(lane, k, nb, T, seg_lo, RL - 1, pm, pr, pi, m);
+        if (gate_open) seg<FULLROW>(lane, k, nb, T, seg_lo, RL - 1, pm, pr, pi, m);
     }
 
     // end of stream.  sync_aa: a gate still open closes at T (sync_aa.py:560-568);

@@ -14,7 +14,7 @@ enum Variant : int {
     V_EXACT, V_FAST_E, V_FAST_E_DO, V_FAST_SCAN, V_FAST_SCAN_DO, V_RTL_WPB, V_PARK_DIRECT, V_ZW64,
     V_ZW64_GRID, V_ZS, V_ZF_ITEMS, V_ZS_PAIR, V_ZS_DEFER, V_ZS_BPL, V_ZS_C, V_ZS_GBLK, V_MC_FUSED,
     V_MC_FUSE_X, V_ZC_SEQ, V_ZC_NODMA, V_BE_FAST, V_MC_PERS, V_FAST_LDS, V_OCC_LDS,
-    V_FAST_RMPAIR, V_FAST_ST_POLICY, V_FAST_HEAD, V_COUNT
+    V_FAST_RMPAIR, V_FAST_ST_POLICY, V_FAST_HEAD, V_FAST_FULL, V_COUNT
 };
 int64_t variant(Variant v);                                     // INT64_MIN when unset
 inline bool variant_is(Variant v, int64_t value) { return variant(v) == value; }
@@ -284,6 +284,8 @@ struct AaFastArgs {
     // OFS_AA_HEAD_RESIDENT (runtime, wave-uniform): P[b][n], M[b][n] of n < min(L, T) already hold +0.0 and
     // the storing aa_fast / aa_stream kernels leave them unwritten; every other kernel ignores it
     int32_t head_resident;
+    // full-stream form of aa_fast_kernel only, set by its launch: the smallest float >= thr
+    float thr32;
 };
 // returns 1 if the fast path handled the call (launched), 0 if not applicable, <0 on error
 int ofs_aa_fast_try(int fmt, int precision, int n_ant, const AaFastArgs& a, hipStream_t st);
