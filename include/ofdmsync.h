@@ -553,6 +553,17 @@ int32_t ofs_zc_detect(const double* corr_mag, int64_t B, int64_t n, int32_t wind
                       double* corr_scaled, double* thresh_scaled, uint8_t* above_threshold,
                       uint8_t* metric_valid, uint8_t* gate_mask, int32_t max_events,
                       int32_t* n_events, int64_t* ev_int, double* ev_peak, void* stream);
+/*
+ * Which kernel ofs_zc_detect launches for streams of n samples (no GPU call): 0 the sequential
+ * one-wave-per-stream kernel (max(hysteresis, 1) < 64, or variant ZC_SEQ), 1 the fused kernel with
+ * register-staged tiles, 2 the fused kernel with LDS-DMA tiles storing events and gate_mask only,
+ * 3 the fused kernel with LDS-DMA tiles and state arrays.  want_state: any of local_sum,
+ * corr_scaled, thresh_scaled is requested; aligned16: corr_mag is 16-byte aligned.  LDS-DMA needs n
+ * and max(window_size, 1) whole multiples of 128, an aligned corr_mag and variant ZC_NODMA unset.
+ * ofs_zc_detect takes its decision from the same function.
+ */
+int32_t ofs_zc_detect_plan(int64_t n, int32_t window_size, int32_t hysteresis, int32_t want_state,
+                           int32_t aligned16);
 
 /* Gate alone on caller-provided flags: replaces zc_v2.detect_zc_peaks (zc_v2.py:374-446). */
 int32_t ofs_zc_gate(const double* corr_mag, const uint8_t* above_threshold, const uint8_t* metric_valid,

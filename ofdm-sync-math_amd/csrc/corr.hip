@@ -1090,6 +1090,7 @@ int ofs_zc_cfar_try(const double* corr_mag, int64_t B, int64_t n, int W, double 
                     double minmag, int reflen, int hyst, double* local_sum, double* corr_scaled,
                     double* thresh_scaled, uint8_t* above, uint8_t* valid, uint8_t* gate_mask, int max_ev,
                     int32_t* n_ev, int64_t* ev, double* ev_v, hipStream_t st);
+int ofs_zc_cfar_plan(int64_t n, int W, int hyst, bool state, bool aligned16);
 
 extern "C" {
 
@@ -1273,6 +1274,11 @@ int32_t ofs_zc_detect(const double* corr_mag, int64_t B, int64_t n, int32_t wind
     if (frc != 0) return frc > 0 ? OFS_OK : frc;
     hipLaunchKernelGGL(zc_detect_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
+}
+
+int32_t ofs_zc_detect_plan(int64_t n, int32_t window_size, int32_t hysteresis, int32_t want_state,
+                           int32_t aligned16) {
+    return ofs_zc_cfar_plan(n, window_size > 1 ? window_size : 1, hysteresis, want_state != 0, aligned16 != 0);
 }
 
 int32_t ofs_zc_gate(const double* corr_mag, const uint8_t* above_threshold, const uint8_t* metric_valid,

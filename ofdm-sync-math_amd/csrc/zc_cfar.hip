@@ -493,22 +493,33 @@ void zc_cfar_kernel(ZcArgs a) {
 
 }  // namespace
 
+// the one dispatch decision of the zc_v2 CFAR + gate (W: the running-sum window, max(1, window_size)):
+// 0 the sequential kernel of corr.hip, 1 the fused kernel with register-staged tiles, 2 with LDS-DMA
+// tiles storing events and gate mask only, 3 with LDS-DMA tiles and the state arrays.  Both the
+// launch below and the query ofs_zc_detect_plan go through it.
+int ofs_zc_cfar_plan(int64_t n, int W, int hyst, bool state, bool aligned16) {
+    const int Hp = hyst > 1 ? hyst : 1;
+    if (Hp < 64 || n <= 0 || ofs::variant_on(ofs::V_ZC_SEQ)) return 0;
+    const bool dma = ZC % 128 == 0 && n % ZC == 0 && W % ZC == 0 && W >= 0 && aligned16 &&
+                     !ofs::variant_on(ofs::V_ZC_NODMA);
+    return !dma ? 1 : state ? 3 : 2;
+}
+
 // fused CFAR + gate for hysteresis >= one chunk; returns 0 when the shape is not covered
 int ofs_zc_cfar_try(const double* corr_mag, int64_t B, int64_t n, int W, double tv, double scale,
                     double minmag, int reflen, int hyst, double* local_sum, double* corr_scaled,
                     double* thresh_scaled, uint8_t* above, uint8_t* valid, uint8_t* gate_mask, int max_ev,
                     int32_t* n_ev, int64_t* ev, double* ev_v, hipStream_t st) {
     const int Hp = hyst > 1 ? hyst : 1;
-    if (Hp < 64 || B <= 0 || n <= 0 || ofs::variant_on(ofs::V_ZC_SEQ)) return 0;
+    const bool state = local_sum || corr_scaled || thresh_scaled;
+    const int plan = B > 0 ? ofs_zc_cfar_plan(n, W, hyst, state, (reinterpret_cast<uintptr_t>(corr_mag) & 15) == 0) : 0;
+    if (plan == 0) return 0;
     ZcArgs a{corr_mag, B, n, W, tv, scale, minmag, reflen, Hp, local_sum, corr_scaled, thresh_scaled,
              above, valid, gate_mask, max_ev, n_ev, ev, ev_v};
     constexpr int SD = OFS_ZC_S, HD = OFS_ZC_H, SR = OFS_ZC_S_REG, HR = OFS_ZC_H_REG;
-    const bool dma = ZC % 128 == 0 && n % ZC == 0 && W % ZC == 0 && W >= 0 &&
-                     (reinterpret_cast<uintptr_t>(corr_mag) & 15) == 0 && !ofs::variant_on(ofs::V_ZC_NODMA);
-    const bool state = local_sum || corr_scaled || thresh_scaled;
     const dim3 gd((unsigned)((B + SD - 1) / SD)), gr((unsigned)((B + SR - 1) / SR));
-    if (dma && state) hipLaunchKernelGGL((zc_cfar_kernel<true, SD, HD, true>), gd, dim3(64 * (1 + HD)), 0, st, a);
-    else if (dma) hipLaunchKernelGGL((zc_cfar_kernel<true, SD, HD, false>), gd, dim3(64 * (1 + HD)), 0, st, a);
+    if (plan == 3) hipLaunchKernelGGL((zc_cfar_kernel<true, SD, HD, true>), gd, dim3(64 * (1 + HD)), 0, st, a);
+    else if (plan == 2) hipLaunchKernelGGL((zc_cfar_kernel<true, SD, HD, false>), gd, dim3(64 * (1 + HD)), 0, st, a);
     else hipLaunchKernelGGL((zc_cfar_kernel<false, SR, HR, false>), gr, dim3(64 * (1 + HR)), 0, st, a);
     return hipGetLastError() == hipSuccess ? 1 : OFS_EHIP;
 }

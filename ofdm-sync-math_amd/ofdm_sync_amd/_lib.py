@@ -141,6 +141,7 @@ def _declare(lib):
         "ofs_row_argmax": (c_int32, [c_int32, P, c_int64, c_int64, P, P, P]),
         "ofs_zc_detect": (c_int32, [P, c_int64, c_int64, c_int32, c_int64, c_int32, c_double, c_int32,
                                     c_int32, P, P, P, P, P, P, c_int32, P, P, P, P]),
+        "ofs_zc_detect_plan": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32]),
         "ofs_zc_gate": (c_int32, [P, P, P, c_int64, c_int64, c_int32, c_int32, P, c_int32, P, P, P,
                                   P]),
         "ofs_debug_set_variant": (c_int32, [ctypes.c_char_p, c_int64]),

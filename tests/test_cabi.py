@@ -115,6 +115,29 @@ def test_argument_validation_without_gpu(lib):
                              None, None, None, None) == -1
 
 
+def test_zc_detect_plan_without_gpu(lib):
+    """ofs_zc_detect_plan is the dispatch decision of ofs_zc_detect and needs no GPU: 0 sequential
+    (max(hysteresis, 1) < 64 or variant ZC_SEQ), 1 register-staged tiles, 2 LDS-DMA events + mask only,
+    3 LDS-DMA with state arrays (n and max(W, 1) whole 128-sample chunks, corr_mag 16-byte aligned, variant
+    ZC_NODMA unset)."""
+    from ofdm_sync_amd import _lib as L
+    L._declare(lib)
+    P = lib.ofs_zc_detect_plan
+    assert lib.ofs_debug_reset_variants() == 0
+    assert P(1024, 128, 256, 0, 1) == 2 and P(1024, 128, 256, 1, 1) == 3
+    assert P(1000, 128, 256, 0, 1) == 1 and P(1000, 128, 256, 1, 1) == 1
+    assert P(1024, 128, 63, 0, 1) == 0 and P(1024, 128, 63, 1, 1) == 0 and P(1024, 128, 64, 0, 1) == 2
+    assert P(1024, 128, 256, 0, 0) == 1 and P(1024, 128, 256, 1, 0) == 1          # misaligned corr_mag
+    assert P(1024, 100, 256, 0, 1) == 1 and P(1024, 0, 256, 0, 1) == 1            # W = max(1, 0) = 1
+    assert P(128, 128, 64, 0, 1) == 2 and P(64, 32, 64, 0, 1) == 1 and P(0, 128, 256, 0, 1) == 0
+    assert lib.ofs_debug_set_variant(b"ZC_NODMA", 1) == 0
+    assert P(1024, 128, 256, 0, 1) == 1 and P(1024, 128, 256, 1, 1) == 1
+    assert lib.ofs_debug_set_variant(b"ZC_SEQ", 1) == 0
+    assert P(1024, 128, 256, 0, 1) == 0
+    assert lib.ofs_debug_reset_variants() == 0
+    assert P(1024, 128, 256, 0, 1) == 2
+
+
 def test_product_path_refuses_cpu():
     """No CPU fallback: the drop-in raises when no GPU is present."""
     import torch
