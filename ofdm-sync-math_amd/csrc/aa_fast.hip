@@ -28,34 +28,12 @@ using namespace ofs;
 
 namespace {
 
-#ifndef OFS_FAST_WG
-#define OFS_FAST_WG 64
-#endif
-constexpr int FAST_WG = OFS_FAST_WG;   // one wave = one stream per workgroup (paired A/B: 2-6 % faster than 256)
-
-// occupancy bound (min waves per SIMD) of the fast kernel; tuning builds set -DOFS_FAST_WAVES=N
-#ifndef OFS_FAST_WAVES
-#define OFS_FAST_WAVES 0
-#endif
-#if OFS_FAST_WAVES > 0
-#define OFS_FAST_BOUNDS __launch_bounds__(FAST_WG, OFS_FAST_WAVES)
-#else
-#define OFS_FAST_BOUNDS __launch_bounds__(FAST_WG)
-#endif
+constexpr int FAST_WG = 64;       // one wave = one stream per workgroup (paired A/B: 2-6 % faster than 256)
 constexpr int TMAX = 1024;        // stream length handled by the fast path
 constexpr int FAST_CAP_LDS = 160 * 1024 / 10;   // occupancy cap of the storing kernel: 10 workgroups per CU (launch)
 // its full-stream form: 7 per CU (the measured value; at most 160 KiB / 7 = 23405, less the allocation granule)
 constexpr int FAST_CAP_LDS_FULL = 23000;
 
-// cache policy knob (tuning builds): LDS-DMA aux bits
-#ifndef OFS_DMA_AUX
-#define OFS_DMA_AUX 0
-#endif
-// stream staging: 0 = LDS-DMA (global_load_lds_dwordx4), 1 = registers, 2 = registers with the loads
-// pinned as inline asm + per-row vmcnt waits (tuning builds; r06b below)
-#ifndef OFS_FAST_STAGE
-#define OFS_FAST_STAGE 1
-#endif
 typedef float nf4 __attribute__((ext_vector_type(4)));
 typedef float nf2 __attribute__((ext_vector_type(2)));
 // complex values as packed fp32 pairs (re, im): products, in-lane partials and window sums issue
@@ -108,35 +86,14 @@ __device__ __forceinline__ void st_rows2(float* span, const float (&a)[2], const
 }
 
 
-// Stream staging (OFS_FAST_STAGE): 1 (default) = every row of the lane's samples is loaded into
-// registers up front, each row's first use waits only for its own loads; 0 = the wave DMAs its
-// stream into a private 8 KiB LDS slice (global_load_lds_dwordx4) and reads rows back with
-// ds_read_b128.  Paired A/B on the same buffers: registers 1-3 % faster (profiles/
-// r01c_staging_ab.log; the SOL probe shows the same 8 % gap between LDS-DMA and register staging
-// of this read/write pattern).  Round 2, with the DMA as inline asm and per-row vmcnt waits (the
-// builtin made the compiler wait for the whole stream before the first row) and 107 instead of
-// 139 VGPRs (4 waves/SIMD): still 3 % slower (0.315 vs 0.305 ms, profiles/r02av_staging_ab.jsonl).
-// Round 6, the loads pinned (OFS_FAST_STAGE=2: inline-asm global_load_dwordx4, per-row vmcnt) so a
-// tight register budget cannot defer them: 105 VGPRs at 4 waves/SIMD, no spills, bit-identical - and
-// more waves are SLOWER, not faster (paired, 9 rotated rounds, profiles/r06b_headline_pinned_loads_
-// waves_ab.jsonl): 3 waves 0.3067 ms (plain) / 0.3082 (pinned), 4 waves 0.3150 (pinned) / 0.3137
-// (plain), 5 waves 0.3283 (pinned).  The kernel is not latency-starved at 3 waves/SIMD.
-// scan-free gate flags in the P/R/M-storing instantiation too (tuning builds: -DOFS_FAST_FF=1)
-#ifndef OFS_FAST_FF
-#define OFS_FAST_FF 0
-#endif
-// tuning builds: 1 = gate machine after the row loop - each row's (M, |P|^2, P) of the gated rows goes to
-// a wave-private LDS slice and the gate runs over them once every row's stores have issued.  Measured
-// (paired, profiles/r05_headline_gate_breakdown.txt): neutral on the headline (0.2937-0.3053 vs
-// 0.2924-0.3056 ms), 5 % slower detect-only (0.107 vs 0.102 ms); default 0 = per row
-#ifndef OFS_FAST_GATE_LATE
-#define OFS_FAST_GATE_LATE 0
-#endif
-// tuning builds: 1 = rows k < MR of the register-staged kernel keep the two P row scans (of exact zeros)
-// the kernel ran until the resident-head change; default 0 = the energy scan alone
-#ifndef OFS_FAST_HEADSCAN
-#define OFS_FAST_HEADSCAN 0
-#endif
+// Stream staging: every row of the lane's samples is loaded into registers up front and each row's
+// first use waits only for its own loads.  Staging through a wave-private LDS slice (LDS-DMA) measured
+// 1-3 % slower (profiles/r01c_staging_ab.log, r02av_staging_ab.jsonl), and pinning the loads to reach
+// more waves per SIMD is slower too: the kernel is not latency-starved at 3 waves/SIMD
+// (profiles/r06b_headline_pinned_loads_waves_ab.jsonl).  The gate machine runs per row: run after the
+// row loop it was neutral on the headline and 5 % slower detect-only
+// (profiles/r05_headline_gate_breakdown.txt).
+//
 // DO: detect-only instantiation (P/R/M/valid not stored, events only: SURVEY §8d); S32: fp32
 // row scans (ofs_common.h row_scan; the detect-only default, issue-bound there); SV: store path of
 // the one-antenna E = 2 storing kernel = 2 * (row-paired R/M stores) + (non-temporal stores, st_out)
@@ -150,9 +107,9 @@ __device__ __forceinline__ void st_rows2(float* span, const float (&a)[2], const
 // AaFastArgs::thr32, and the gate machine is chosen at launch: FS = 1 the scan-free rows (max(hyst, 1)
 // >= RL), FS = 2 the scan rows - not both bodies inline behind a per-row test.
 template <int E, int MR, int NA, bool DO, bool S32, int SV = 0, int FS = 0>
-__global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
+__global__ __launch_bounds__(FAST_WG) void aa_fast_kernel(AaFastArgs a) {
     static_assert(SV == 0 || (E == 2 && NA == 1 && !DO), "store-path variants: one-antenna E = 2 storing kernel");
-    static_assert(FS == 0 || (SV == 3 && !S32 && OFS_FAST_STAGE == 1 && !OFS_FAST_GATE_LATE), "full-stream form: the headline's kernel");
+    static_assert(FS == 0 || (SV == 3 && !S32), "full-stream form: the headline's kernel");
     constexpr bool FULL = FS != 0;
     constexpr int SP = SV & 1;                 // output store cache policy
     constexpr bool RP = (SV & 2) != 0;         // R/M of rows k, k+1 (k even) as one 16-byte store per lane
@@ -161,81 +118,21 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
     constexpr int L = MR * RL;
     constexpr int V4 = E / 2;                  // float4 (2 samples) per lane per row
     static_assert(MR >= 1 && MR <= RW, "window must fit the stream tile");
-#if OFS_FAST_STAGE == 0
-    __shared__ float4 lds[FAST_WG / 64][NA * RW * V4][64];
-#endif
     const int lane = threadIdx.x & 63;
-    // (FULL: one wave per workgroup is wave 0, which keeps the stream index and every base scalar)
-    const int w = (FULL && FAST_WG == 64) ? 0 : threadIdx.x >> 6;
+    // the wave index is 0 (one wave per workgroup), but the compiler does not know it: the term keeps the
+    // stream index of the generic form in a VGPR.  Without it the index is wave-uniform, all 142
+    // instantiations compile differently and detect-only measured 1-2 % slower (0.0943-0.0949 against
+    // 0.0930-0.0936 ms, profiles/aa_fast_rowsums_candidates.txt)
+    const int w = FULL ? 0 : threadIdx.x >> 6;
     // block order: one antenna plain blockIdx, two the XCD remap (paired under the occupancy cap,
     // profiles/r06n_headline_remap_ff_ab.txt: without the remap cfg3 0.2994 -> 0.2940 ms, detect-only
     // 0.1036 -> 0.0949, T 4096 1.225 -> 1.211; two antennas 0.4004 -> 0.4055 and the 2 x 5315 shape
     // slower in 2 of 3 rounds - they keep it)
-    const int64_t b = (int64_t)(NA == 1 ? blockIdx.x : xcd_block()) * (FAST_WG / 64) + w;
+    const int64_t b = (int64_t)(NA == 1 ? blockIdx.x : xcd_block()) + w;
     if (b >= a.B) return;
     const int T = FULL ? TMAX : (int)a.T;
     // FULL: byte offset of this lane's 16 bytes in a row of x / P and in a row pair of R / M
     const uint32_t lo16 = 16u * (uint32_t)lane;
-#if OFS_FAST_STAGE == 0
-    // row-major DMA order (row k of every antenna before row k+1): row k has landed once at most
-    // the later rows' DMAs and the output stores of rows < k (SPR per row, all younger) are
-    // outstanding - vmcnt counts in order.  The DMA goes through inline asm (ofs::lds_dma16): the
-    // builtin makes the compiler wait for every DMA before the first LDS read.  Event stores are
-    // not counted (a larger count could only under-wait; a smaller one waits longer).
-    constexpr int SPR = V4 + ((E % 4 != 0) ? 2 * V4 : 2 * (V4 / 2));   // P + R + M stores per row
-#pragma unroll
-    for (int k = 0; k < RW; ++k)
-#pragma unroll
-        for (int t = 0; t < NA; ++t) {
-            const float2* xs = reinterpret_cast<const float2*>(a.x) + (b * NA + t) * a.T;
-#pragma unroll
-            for (int j = 0; j < V4; ++j) {
-                int n = RL * k + E * lane + 2 * j;
-                n = n < T ? n : T - 2;                          // in-bounds; zeroed on read
-                ofs::lds_dma16(xs + n, &lds[w][(t * RW + k) * V4 + j][0]);
-            }
-        }
-    auto ldrow = [&](int t, int k, int j) { return lds[w][(t * RW + k) * V4 + j][lane]; };
-    // SPR counts only when all of P, R, M are stored (uncounted stores only make the wait longer)
-    const bool all_out = !DO && !RP && a.P && a.R && a.M;      // (paired R/M stores: not counted)
-    auto row_wait = [&](int k) {
-        if (all_out) ofs::vmcnt_wait((RW - 1 - k) * NA * V4 + k * SPR);
-        else ofs::vmcnt_wait((RW - 1 - k) * NA * V4);
-    };
-#elif OFS_FAST_STAGE == 2
-    // register staging with the loads PINNED at the top: each load is an inline-asm
-    // global_load_dwordx4 (the compiler cannot sink it under a tight register budget, which is
-    // what the plain loads did at 4 waves/SIMD), each row's first use waits with its own
-    // s_waitcnt vmcnt(n) - n = the younger operations still allowed in flight, vmcnt counting
-    // in order: the loads of later rows, plus, for a full stream (T = TMAX, every row's stores
-    // issued by every lane) with P, R and M all stored, the SPR stores of each earlier row.  Any
-    // other shape counts the loads alone (the stores then only lengthen the wait).  An empty asm
-    // that rewrites the row's registers right after the wait keeps their uses behind it.
-    constexpr int SPR = V4 + ((E % 4 != 0) ? 2 * V4 : 2 * (V4 / 2));   // P + R + M stores per row
-    nf4 xreg[NA][RW][V4];
-#pragma unroll
-    for (int k = 0; k < RW; ++k)
-#pragma unroll
-        for (int t = 0; t < NA; ++t) {
-            const float2* xs = reinterpret_cast<const float2*>(a.x) + (b * NA + t) * a.T;
-#pragma unroll
-            for (int j = 0; j < V4; ++j) {
-                int n = RL * k + E * lane + 2 * j;
-                n = n < T ? n : T - 2;                          // in-bounds; zeroed on read
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xreg[t][k][j]) : "v"(xs + n) : "memory");
-            }
-        }
-    const bool count_st = !DO && !RP && a.P && a.R && a.M && T == TMAX;
-    auto ldrow = [&](int t, int k, int j) { const nf4 v = xreg[t][k][j]; return make_float4(v.x, v.y, v.z, v.w); };
-    auto row_wait = [&](int k) {
-        if (count_st) ofs::vmcnt_wait((RW - 1 - k) * NA * V4 + k * SPR);
-        else ofs::vmcnt_wait((RW - 1 - k) * NA * V4);
-#pragma unroll
-        for (int t = 0; t < NA; ++t)
-#pragma unroll
-            for (int j = 0; j < V4; ++j) asm volatile("" : "+v"(xreg[t][k][j]));
-    };
-#else
     // register staging: every row of the lane's samples is loaded up front (RW * V4 float4), each
     // row's first use waits only for its own loads (vmcnt counts in order)
     float4 xreg[NA][RW][V4];
@@ -245,26 +142,23 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
         for (int k = 0; k < RW; ++k) xreg[0][k][0] = *reinterpret_cast<const float4*>(xb + RL * 8 * k + lo16);
     } else {
 #pragma unroll
-    for (int t = 0; t < NA; ++t) {
-        const float2* xs = reinterpret_cast<const float2*>(a.x) + (b * NA + t) * a.T;
+        for (int t = 0; t < NA; ++t) {
+            const float2* xs = reinterpret_cast<const float2*>(a.x) + (b * NA + t) * a.T;
 #pragma unroll
-        for (int k = 0; k < RW; ++k)
+            for (int k = 0; k < RW; ++k)
 #pragma unroll
-            for (int j = 0; j < V4; ++j) {
-                int n = RL * k + E * lane + 2 * j;
-                n = n < T ? n : T - 2;                          // in-bounds; zeroed on read
-                xreg[t][k][j] = *reinterpret_cast<const float4*>(xs + n);
-            }
+                for (int j = 0; j < V4; ++j) {
+                    int n = RL * k + E * lane + 2 * j;
+                    n = n < T ? n : T - 2;                      // in-bounds; zeroed on read
+                    xreg[t][k][j] = *reinterpret_cast<const float4*>(xs + n);
+                }
+        }
     }
-    }
-    auto ldrow = [&](int t, int k, int j) { return xreg[t][k][j]; };
-    auto row_wait = [&](int) {};
-#endif
     auto xrow = [&](int t, int k, pf2 (&c)[E]) {
 #pragma unroll
         for (int j = 0; j < V4; ++j) {
             const bool ok = FULL || RL * k + E * lane + 2 * j < T;
-            const float4 v = ldrow(t, k, j);
+            const float4 v = xreg[t][k][j];
             c[2 * j] = ok ? pf2{v.x, v.y} : pf2{0.f, 0.f};
             c[2 * j + 1] = ok ? pf2{v.z, v.w} : pf2{0.f, 0.f};
         }
@@ -277,11 +171,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
 
     // scan-free gate flags: detect-only, and the one-antenna storing kernel (round 6, under the occupancy
     // cap: 0.2905 -> 0.2889 ms, 0.2979 -> 0.2966 with the remap; r06m / r06n)
-    AaRowGate<E, float, false, (bool)(DO || OFS_FAST_FF || NA == 1)> gate;   // event state (wave-uniform)
-#if OFS_FAST_GATE_LATE
-    constexpr int GR = RW - MR > 0 ? RW - MR : 1;             // gated rows (k >= MR)
-    __shared__ float4 gl[FAST_WG / 64][GR][E][64];            // (M, |P|^2, Re P, Im P) per sample
-#endif
+    AaRowGate<E, float, false, (bool)(DO || NA == 1)> gate;   // event state (wave-uniform)
     const bool detect = FULL || a.detect;
     if (detect)
         gate.init(a.hyst, L, a.thr, a.fs, a.max_ev, a.ev_i + b * (int64_t)a.max_ev * 4,
@@ -311,7 +201,6 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
             float aE[E];
 #pragma unroll
             for (int e = 0; e < E; ++e) { av[e] = pf2{0.f, 0.f}; aE[e] = 0.f; }
-            row_wait(k);
 #pragma unroll
             for (int t = 0; t < NA; ++t) {
                 pf2 c[E];
@@ -340,7 +229,7 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
             // are +0.0 - only the energy is scanned there (the same bits: a scan of zeros gives +0.0)
             const RowScan sEr = row_scan<S32>(fE[E - 1]);
             RowScan sRr{0.f, 0.f, 0.0}, sIr{0.f, 0.f, 0.0};
-            if (k >= MR || OFS_FAST_HEADSCAN) { sRr = row_scan<S32>(fS[E - 1].x); sIr = row_scan<S32>(fS[E - 1].y); }
+            if (k >= MR) { sRr = row_scan<S32>(fS[E - 1].x); sIr = row_scan<S32>(fS[E - 1].y); }
             const double totR = sRr.tot, totI = sIr.tot, totE = sEr.tot;
             const pf2 xS = pf2{sRr.x, sIr.x};                        // lanes < l
             const float xE = sEr.x;
@@ -422,10 +311,6 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
 
             // ---- events: closed-form gate machine, streamed per row (aa_gate.h) ----
             if (detect && k >= MR) {
-#if OFS_FAST_GATE_LATE
-#pragma unroll
-                for (int e = 0; e < E; ++e) gl[w][k >= MR ? k - MR : 0][e][lane] = make_float4(mf[e], pmf[e], pf[e][0], pf[e][1]);
-#else
                 float pr[E], pi[E];
 #pragma unroll
                 for (int e = 0; e < E; ++e) { pr[e] = pf[e][0]; pi[e] = pf[e][1]; }
@@ -438,29 +323,9 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
                 } else {
                     gate.row(lane, k, nb, T, mf, pmf, pr, pi);
                 }
-#endif
             }
         }
     }
-#if OFS_FAST_GATE_LATE
-    if (a.detect) {
-        // this wave's own LDS slice, written lane-wise above: a wave-local hand-over
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll 1
-        for (int k = MR; k < RW; ++k) {
-            if (RL * k >= T) break;
-            float m[E], pm[E], pr[E], pi[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const float4 v = gl[w][k - MR][e][lane];
-                m[e] = v.x; pm[e] = v.y; pr[e] = v.z; pi[e] = v.w;
-            }
-            gate.row(lane, k, RL * k + E * lane, T, m, pm, pr, pi);
-        }
-    }
-#endif
     if (detect) gate.finish(lane, T, a.n_ev + b);
 }
 
@@ -479,38 +344,10 @@ __global__ OFS_FAST_BOUNDS void aa_fast_kernel(AaFastArgs a) {
 typedef float f4u __attribute__((ext_vector_type(4), aligned(8)));
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 
-#ifndef OFS_STREAM_WG
-#define OFS_STREAM_WG 64
-#endif
-constexpr int STREAM_WG = OFS_STREAM_WG;
-// tuning builds: rows in flight (OFS_STREAM_PD), occupancy bound (OFS_STREAM_WAVES waves/SIMD)
-#ifndef OFS_STREAM_PD
-#define OFS_STREAM_PD 0
-#endif
-#ifndef OFS_STREAM_WAVES
-#define OFS_STREAM_WAVES 0
-#endif
 // workgroup size of the streaming kernel: the one-antenna storing kernel runs 2 streams per workgroup
 // (round 6, paired, profiles/r06v_stream_kernel_variants_ab.txt: T 4096 1.222 -> 1.192 ms); two
 // antennas (the 2 x 5315 reference shape: 0.578 vs 0.608 ms) and detect-only keep one
-#ifndef OFS_STREAM_WG1
-#define OFS_STREAM_WG1 128
-#endif
-constexpr int stream_wg(int na, bool det_only) { return (na == 1 && !det_only) ? OFS_STREAM_WG1 : STREAM_WG; }
-#if OFS_STREAM_WAVES > 0
-#define OFS_STREAM_BOUNDS __launch_bounds__(stream_wg(NA, DO), OFS_STREAM_WAVES)
-#else
-#define OFS_STREAM_BOUNDS __launch_bounds__(stream_wg(NA, DO))
-#endif
-
-#ifndef OFS_STREAM_FF
-#define OFS_STREAM_FF 1
-#endif
-// lag ring (raw samples of rows k-MR..k-1) in a wave-private LDS slice instead of VGPRs:
-// 0 = never, 1 = two antennas (frees 32 VGPRs there), 2 = always
-#ifndef OFS_STREAM_LDSLAG
-#define OFS_STREAM_LDSLAG 1
-#endif
+constexpr int stream_wg(int na, bool det_only) { return (na == 1 && !det_only) ? 128 : 64; }
 
 // per-wave state of the streaming kernel; row<U, FIRST, GUARD>() processes row k whose ring
 // position k mod PER == U is a compile-time constant: FIRST = rows k < MR (no lagged product,
@@ -523,9 +360,11 @@ struct AaStream {
     // rows in flight ahead of use (paired A/B, tools/lib_ab.py, r02e: 1 antenna PD 2, 2 antennas
     // with the LDS lag ring PD 4; the peeled steady loop + scan-free gate flags + these took the
     // T = 4096 shape 1.32 -> 1.09 ms and the 2 x 5315 reference shape 0.75 -> 0.49 ms)
-    static constexpr int PD = OFS_STREAM_PD > 0 ? OFS_STREAM_PD : ((E == 2 && NA == 2) ? 4 : 2);
+    static constexpr int PD = (E == 2 && NA == 2) ? 4 : 2;
     static constexpr int PER = MR > PD ? MR : PD;            // unroll period (MR, PD powers of 2)
-    static constexpr bool LDSLAG = OFS_STREAM_LDSLAG == 2 || (OFS_STREAM_LDSLAG == 1 && NA == 2);
+    // lag ring (raw samples of rows k-MR..k-1) in a wave-private LDS slice instead of VGPRs: two
+    // antennas (frees 32 VGPRs there)
+    static constexpr bool LDSLAG = NA == 2;
 
     const float2* xb;
     float4 (*lag)[NA][V4][64];                               // LDSLAG: [MR][NA][V4][lane]
@@ -537,7 +376,7 @@ struct AaStream {
     double cbR[MR], cbI[MR], cbE[MR];                        // row bases C[j], j in (k-MR, k]
     double CR, CI, CE;                                       // C[k]: prefix at the start of row k
     float2 nx[PD][NA][E];                                    // rows k..k+PD-1 in flight
-    AaRowGate<E, float, false, (bool)(DO || OFS_STREAM_FF)> gate;
+    AaRowGate<E, float, false, true> gate;
     float2* Pout; float* Rout; float* Mout; uint8_t* Vout;
     bool detect, head;                                       // head: P, M of n < L resident (not stored)
     float floor_;
@@ -594,6 +433,11 @@ struct AaStream {
                 }
             }
         }
+        // From here to the row bases: aa_fast_kernel's row sums, expression for expression (the tests hold
+        // the kernels bit-identical to each other, so the two copies move together).  One shared function
+        // was built and measured: bit-identical, but the two-antenna kernel here ran 0.4-0.5 % slower in
+        // every round and three aa_fast_kernel instantiations lost a wave per SIMD
+        // (profiles/aa_fast_rowsums_candidates.txt).
         // ---- lagged products x[n]·conj(x[n-L]) and energies, summed over the antennas ----
         pf2 av[E];
         float aE[E];
@@ -691,7 +535,7 @@ struct AaStream {
 };
 
 template <int E, int MR, int NA, bool DO>
-__global__ OFS_STREAM_BOUNDS void aa_stream_kernel(AaFastArgs a) {
+__global__ __launch_bounds__(stream_wg(NA, DO)) void aa_stream_kernel(AaFastArgs a) {
     using S = AaStream<E, MR, NA, DO>;
     constexpr int SWG = stream_wg(NA, DO);
     __shared__ float4 lagbuf[SWG / 64][S::LDSLAG ? MR : 1][NA][S::V4][64];
@@ -764,13 +608,17 @@ int launch_stream(const AaFastArgs& a, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 1 : OFS_EHIP;
 }
 
+// ofs_aa_fast_plan tries E = 2 first, so E = 4 is reached only by L = 2048 (MR = 8): its other
+// windows are not instantiated (0: the general engine)
 template <int E, int NA>
 int launch_stream_mr(int mr, const AaFastArgs& a, hipStream_t st) {
-    switch (mr) {
-        case 1: return launch_stream<E, 1, NA>(a, st);
-        case 2: return launch_stream<E, 2, NA>(a, st);
-        case 4: return launch_stream<E, 4, NA>(a, st);
-        case 8: return launch_stream<E, 8, NA>(a, st);
+    if (mr == 8) return launch_stream<E, 8, NA>(a, st);
+    if constexpr (E == 2) {
+        switch (mr) {
+            case 1: return launch_stream<E, 1, NA>(a, st);
+            case 2: return launch_stream<E, 2, NA>(a, st);
+            case 4: return launch_stream<E, 4, NA>(a, st);
+        }
     }
     return 0;
 }
@@ -802,7 +650,7 @@ template <int E, int MR, int NA>
 int launch(const AaFastArgs& a, hipStream_t st) {
     const bool det_only = a.detect && !a.P && !a.R && !a.M && !a.valid;
     const bool s32 = scan32(det_only);
-    const dim3 grid((unsigned)((a.B + FAST_WG / 64 - 1) / (FAST_WG / 64))), blk(FAST_WG);
+    const dim3 grid((unsigned)a.B), blk(FAST_WG);            // one wave = one stream per workgroup
     // Occupancy cap: the P/R/M-storing one-antenna kernel runs 10 workgroups (waves) per CU instead
     // of the 12 its 139 VGPRs allow, through 16 KiB of unused dynamic LDS per workgroup (160 KiB per
     // CU / 10).  Paired, 11 rotated rounds on the headline (profiles/r06d_headline_occupancy_sweep.json):

@@ -20,32 +20,11 @@
 
 namespace ofs {
 
-// gate machine variants (paired A/B builds): scan-free flags when H >= RL (template FF: on for
-// the fp64 kernels and the detect-only fp32 kernel - 5-8 % there - off for the fp32 kernel that
-// also stores P/R/M, where it measured 1-2 % slower); per-lane peak tracking reduced over the
+// gate machine forms, chosen per kernel: scan-free flags when H >= RL (template FF: on for the
+// fp64 kernels and the detect-only fp32 kernel - 5-8 % there - off for the two-antenna fp32 kernel
+// that also stores P/R/M, where it measured 1-2 % slower); per-lane peak tracking reduced over the
 // wave once per event instead of once per row (template DEFER; neutral on the headline, off
 // for the complex128 kernel whose extra fp64 lane state cost it occupancy)
-#ifndef OFS_GATE_FASTFLAGS
-#define OFS_GATE_FASTFLAGS 1
-#endif
-#ifndef OFS_GATE_PRED
-#define OFS_GATE_PRED 0
-#endif
-#ifndef OFS_GATE_NOINLINE_EMIT
-#define OFS_GATE_NOINLINE_EMIT 0
-#endif
-#ifndef OFS_GATE_FFONLY
-#define OFS_GATE_FFONLY 0
-#endif
-#ifndef OFS_GATE_DIAG
-#define OFS_GATE_DIAG 0
-#endif
-#ifndef OFS_GATE_NOACC
-#define OFS_GATE_NOACC 0
-#endif
-#ifndef OFS_GATE_DEFER
-#define OFS_GATE_DEFER 1
-#endif
 
 constexpr int GATE_NOKEY = 1 << 20;      // row-relative keys
 constexpr int ABS_NOKEY = 0x7fffffff;    // absolute sample indices
@@ -82,11 +61,7 @@ struct AaRowGate : AaGateAbs<ABS> {
     // the record is wave-uniform: lanes 0..3 store the four int64 fields and lanes 4..7 the four
     // f64 fields, one store instruction per 32-byte record half (a lane-0 loop of 8-byte stores
     // cost ~450 B of write traffic per event, measured with WRITE_SIZE)
-#if OFS_GATE_NOINLINE_EMIT
-    __device__ __attribute__((noinline)) void emit(int lane, int gate_end) {
-#else
     __device__ __forceinline__ void emit(int lane, int gate_end) {
-#endif
         if (evi && n_ev < max_ev && lane < 8) {
             int64_t* ei = evi + (int64_t)n_ev * 4;
             if constexpr (RTL) {
@@ -113,19 +88,9 @@ struct AaRowGate : AaGateAbs<ABS> {
     // sync_aa row (all positions >= L): above = m >= threshold; m = metric, pm = |P|², pr/pi = P
     __device__ __forceinline__ void row(int lane, int k, int nb, int T, const V (&m)[E], const V (&pm)[E],
                                         const V (&pr)[E], const V (&pi)[E]) {
-#if OFS_GATE_DIAG == 1              // diagnostic builds only (wrong events): no row work at all
-        return;
-#endif
         bool ab[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) ab[e] = (nb + e < T) && (double)m[e] >= thr;
-#if OFS_GATE_DIAG == 2              // diagnostic builds only: the above ballots, nothing else
-        uint64_t any = 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) any |= __ballot(ab[e]);
-        if (any) carry_last = RL * k;
-        return;
-#endif
         row_flags(lane, k, nb, T, ab, pm, pr, pi, m);
     }
 
@@ -141,28 +106,17 @@ struct AaRowGate : AaGateAbs<ABS> {
     template <bool FULLROW = false>
     __device__ __forceinline__ void accumulate(int lane, int k, int nb, int T, int lo, int hi, const V (&pm)[E],
                                                const V (&pr)[E], const V (&pi)[E], const V (&m)[E]) {
-#if OFS_GATE_NOACC == 1             // diagnostic builds only (wrong peaks): no per-lane peak tracking
-        return;
-#endif
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int key = E * lane + e;
             const bool in = (FULLROW || nb + e < T) && key >= lo && key <= hi;
             const bool better = RTL ? (pm[e] >= lv) : (pm[e] > lv);
-#if OFS_GATE_NOACC == 2             // diagnostic builds only (wrong payload): value + index tracked
-            if (in && better) { lv = pm[e]; lk = RL * k + key; }
-#else
             if (in && better) { lv = pm[e]; lk = RL * k + key; lpr = pr[e]; lpi = pi[e]; lm = m[e]; }
-#endif
         }
     }
     // wave reduction of the lanes' running bests into the event's peak (kept if it beats the
     // peak so far under the machine's tie rule), then the lanes restart
-#if OFS_GATE_NOINLINE_EMIT
-    __device__ __attribute__((noinline)) void merge() {
-#else
     __device__ __forceinline__ void merge() {
-#endif
         const V vmax = wave_max(lv);
         const int kk = RTL ? wave_max_i(lv == vmax ? lk : -1) : wave_min(lv == vmax ? lk : ABS_NOKEY);
         const bool found = RTL ? (kk >= 0) : (kk != ABS_NOKEY);
@@ -177,12 +131,12 @@ struct AaRowGate : AaGateAbs<ABS> {
         }
         lane_reset();
     }
-    // a gate's samples within one row; OFS_GATE_DEFER = 0 reduces over the wave every row
+    // a gate's samples within one row; DEFER = false reduces over the wave every row
     template <bool FULLROW = false>
     __device__ __forceinline__ void seg(int lane, int k, int nb, int T, int lo, int hi, const V (&pm)[E],
                                         const V (&pr)[E], const V (&pi)[E], const V (&m)[E]) {
         accumulate<FULLROW>(lane, k, nb, T, lo, hi, pm, pr, pi, m);
-        if (!(DEFER && OFS_GATE_DEFER)) merge();
+        if (!DEFER) merge();
     }
     __device__ __forceinline__ void open_at(int start) {
         gate_open = 1; ev_start = start; bpm = (V)-1; lane_reset();
@@ -197,41 +151,7 @@ struct AaRowGate : AaGateAbs<ABS> {
     __device__ __forceinline__ void row_flags(int lane, int k, int nb, int T, const bool (&ab)[E],
                                               const V (&pm)[E], const V (&pr)[E], const V (&pi)[E],
                                               const V (&m)[E]) {
-#if OFS_GATE_PRED
-        if (FF && DEFER && OFS_GATE_DEFER && Hp >= RL) {
-            // the scan-free machine with the common path predicated: the only branch left per row is
-            // the (rare) gate close; opening, the carry and the per-lane peak tracking are selects
-            int first = GATE_NOKEY, last = -1;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const uint64_t am = __ballot(ab[e]);
-                const int f = am ? E * (int)__builtin_ctzll(am) + e : GATE_NOKEY;
-                const int l = am ? E * (63 - (int)__builtin_clzll(am)) + e : -1;
-                first = min(first, f);
-                last = max(last, l);
-            }
-            const int base = RL * k;
-            const int c = carry_last + Hp;
-            if (carry_last >= 0 && c >= base && c < base + RL && c < T && c - base < first) {
-                accumulate(lane, k, nb, T, gate_open ? 0 : -1, c - base, pm, pr, pi, m);
-                merge();
-                emit(lane, c);
-                gate_open = 0;
-            }
-            const bool has = first != GATE_NOKEY;
-            const bool opens = has && (carry_last < 0 || base + first - 1 - carry_last >= Hp);
-            carry_last = has ? base + last : carry_last;
-            ev_start = opens ? base + first : ev_start;
-            bpm = opens ? (V)-1 : bpm;
-            lv = opens ? (V)-1 : lv;
-            lk = opens ? (RTL ? -1 : ABS_NOKEY) : lk;
-            const int lo = opens ? first : (gate_open ? 0 : RL);    // RL: empty range (gate closed)
-            gate_open = (opens || gate_open) ? 1 : 0;
-            accumulate(lane, k, nb, T, lo, RL - 1, pm, pr, pi, m);
-            return;
-        }
-#endif
-        if (MODE == 1 || (MODE == 0 && FF && OFS_GATE_FASTFLAGS && (OFS_GATE_FFONLY || Hp >= RL))) {
+        if (MODE == 1 || (MODE == 0 && FF && Hp >= RL)) {
             // hysteresis at least one row: only the row's FIRST above sample can open a gate and
             // only carry_last + Hp can close one (before that first sample), so the machine runs
             // on the above ballots alone, in scalar registers - no prefix scan
@@ -250,7 +170,7 @@ struct AaRowGate : AaGateAbs<ABS> {
                 const int c = carry_last + Hp;
                 if (c >= base && c < base + RL && (FULLROW || c < T) && c - base < first) {
                     seg<FULLROW>(lane, k, nb, T, seg_lo, c - base, pm, pr, pi, m);
-                    if (DEFER && OFS_GATE_DEFER) merge();
+                    if (DEFER) merge();
                     emit(lane, c);
                     gate_open = 0; seg_lo = -1;
                 }
@@ -265,9 +185,6 @@ struct AaRowGate : AaGateAbs<ABS> {
             if (gate_open) seg<FULLROW>(lane, k, nb, T, seg_lo, RL - 1, pm, pr, pi, m);
             return;
         }
-#if OFS_GATE_FFONLY                 // diagnostic builds only (H >= one row assumed): no scan path
-        return;
-#endif
         int lane_last = -1;
 #pragma unroll
         for (int e = 0; e < E; ++e)
@@ -308,7 +225,7 @@ struct AaRowGate : AaGateAbs<ABS> {
                     open_at(RL * k + key); seg_lo = key;
                 } else {
                     seg<FULLROW>(lane, k, nb, T, seg_lo, key, pm, pr, pi, m);
-                    if (DEFER && OFS_GATE_DEFER) merge();
+                    if (DEFER) merge();
                     emit(lane, RL * k + key);
                     gate_open = 0; seg_lo = -1;
                 }
@@ -327,7 +244,7 @@ struct AaRowGate : AaGateAbs<ABS> {
                 if (open_start) *open_start = gate_open ? ev_start : -1;
             }
         } else {
-            if (gate_open) { if (DEFER && OFS_GATE_DEFER) merge(); emit(lane, T); }
+            if (gate_open) { if (DEFER) merge(); emit(lane, T); }
             if (lane == 0) *n_ev_out = n_ev;
         }
     }

@@ -21,8 +21,12 @@ def lib():
     if _lib is None:
         src = os.path.join(_HERE, "csrc", "ofs_oracle.c")
         if not os.path.exists(LIB) or os.path.getmtime(LIB) < os.path.getmtime(src):
-            subprocess.run(["gcc", "-O2", "-fopenmp", "-fPIC", "-shared", "-std=c11", "-o", LIB, src, "-lm"],
+            # built under a name of this process's own and moved into place whole: ranks of one test start
+            # together, and a rank must never load the file another is still writing
+            tmp = f"{LIB}.{os.getpid()}.tmp"
+            subprocess.run(["gcc", "-O2", "-fopenmp", "-fPIC", "-shared", "-std=c11", "-o", tmp, src, "-lm"],
                            check=True)
+            os.replace(tmp, LIB)
         l = ctypes.CDLL(LIB)
         l.oracle_aa_detect.restype = c_int
         l.oracle_aa_detect.argtypes = [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_double,

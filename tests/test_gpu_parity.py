@@ -456,7 +456,7 @@ def test_aa_fast_path_sweep(L, T):
 
 
 @pytest.mark.parametrize("na", [1, 2])
-@pytest.mark.parametrize("L", [128, 256, 512, 1024])
+@pytest.mark.parametrize("L", [128, 256, 512, 1024, 2048])
 @pytest.mark.parametrize("T", [1025, 1536, 2047, 4096, 5315])
 def test_aa_stream_path_sweep(T, L, na):
     """Streaming wave-per-stream kernel (any T, odd T included: 8-byte-aligned stream bases)

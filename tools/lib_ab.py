@@ -53,8 +53,12 @@ def main():
         P[:, :min(L, T)].zero_()
         M[:, :min(L, T)].zero_()
     n_ev = torch.zeros(B, dtype=torch.int32, device=dev)
-    ev_i = torch.empty((B, E, 4), dtype=torch.int64, device=dev)
-    ev_r = torch.empty((B, E, 4), dtype=torch.float64, device=dev)
+    ev_i = torch.zeros((B, E, 4), dtype=torch.int64, device=dev)       # records past n_ev are never written
+    ev_r = torch.zeros((B, E, 4), dtype=torch.float64, device=dev)
+    # every output compared bit for bit between the libraries (the stored ones)
+    outs = {k: v for k, v in dict(n_ev=n_ev, ev_i=ev_i, ev_r=ev_r, P=P, R=R, M=M).items() if v is not None}
+    bits = lambda t: torch.view_as_real(t).view(torch.int32) if t.is_complex() else t.view(
+        torch.int64 if t.element_size() == 8 else torch.int32)
     st = torch.cuda.current_stream(dev)
     libs = []
     for p in a.libs.split(","):
@@ -81,11 +85,10 @@ def main():
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / a.steps)
             if ref is None:
-                ref = (n_ev.clone(), None if M is None else M.clone())
+                ref = {k: bits(v).clone() for k, v in outs.items()}
             elif not a.no_check:
-                assert torch.equal(ref[0], n_ev), f"{name}: events differ"
-                if M is not None:
-                    assert torch.equal(ref[1], M), f"{name}: M differs"
+                for k, v in outs.items():
+                    assert torch.equal(ref[k], bits(v)), f"{name}: {k} differs"
     alg = B * T * (na * 8 + (0 if a.detect_only else 16))
     for name, _ in libs:
         ms = statistics.median(times[name])

@@ -1,7 +1,7 @@
 """Build tuning variants of libofdmsync.so: only the translation units whose flags change are
 recompiled per variant; the others are compiled once.  Diagnostic tooling (not the product).
 
-    python tools/variants.py aa_fast.hip "pd2=-DOFS_STREAM_PD=2" "w4=-DOFS_STREAM_WAVES=4" ...
+    python tools/variants.py win_fast.hip "w4=-DOFS_SCM_WAVES=4" "wg2=-DOFS_SCM_WG2=1" ...
 Writes build/libofdmsync_<name>.so (load one with `OFS_LIB=... python tools/<tool>.py`: the tools pass it to
 _lib.use_tuning_library, which accepts only a library whose baked hash reads variant-<name>).
 """
