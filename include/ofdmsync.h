@@ -271,6 +271,65 @@ int32_t ofs_minn_rtl(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int
 int32_t ofs_rtl_plan(int32_t in_fmt, int32_t n_br, int64_t T, int32_t Q);
 
 /*
+ * Resumable chunked minn_rtl detection for integer streams of any length (no reference counterpart:
+ * the reference's sample-by-sample models, minn_rtl.py:583-825, are the specification).
+ *
+ * A stream is fed in consecutive chunks of Tc samples; ofs_minn_rtl_chunk returns the chunk's eight
+ * metric arrays and the gate events that CLOSED among its samples, and keeps what the next call needs
+ * (the last 3Q samples, the IIR state, the gate machine) in a caller-owned state buffer on the device.
+ * The library allocates nothing and keeps no global state.
+ *   in_fmt  OFS_CI16: x = [B][n_br][Tc] int16 (I, Q);  OFS_CP12: x = [B][Tc][3 * n_br] bytes.
+ *           n_br 1-2; Q 64, 128, 256 or 512 (the table of the integer-exact one-shot kernel).
+ *   state   [B][ofs_rtl_chunk_state_bytes(n_br, Q)] bytes, 16-byte aligned, device memory.  The layout
+ *           is opaque; ALL-ZERO BYTES ARE A FRESH STREAM, so any subset of streams is reset with a
+ *           memset of its rows (stream-ordered with the calls).  One state row belongs to one stream:
+ *           in_fmt, n_br, Q, smooth_shift, smooth_mode, threshold_value, threshold_frac_bits,
+ *           hysteresis, timing_offset and detect must not change between the calls of a stream
+ *           (max_events and which arrays are requested may), and the calls of a stream must be ordered
+ *           (same HIP stream, or synchronised by the caller).
+ *   corr_total .. above_threshold  [B][Tc], f64 / uint8 as in ofs_minn_rtl, EACH nullable; index i of a
+ *           call is the stream's absolute sample n = (samples of earlier calls) + i.  The fill phase
+ *           (taps valid from n = Q-1, 2Q-1, 3Q-1; metric_valid = n >= 3Q-1) is decided on n, so a chunk
+ *           edge may fall anywhere.  smooth_metric at a sample that is not valid yet is the held state.
+ *   events  [B][max_events][4] int64 = peak, peak + timing_offset, seg_start, seg_end, ABSOLUTE indices,
+ *           written from slot 0 of every call while n_events < max_events; n_events[b] is the number of
+ *           gates that closed during this call (exact even above max_events).  The peak is the LAST
+ *           maximum of corr_positive in the gate (>=), across calls too.  A gate still open at the end
+ *           of the chunk is carried, over any number of calls.  As in ofs_minn_rtl it is never closed
+ *           at the end of the stream: every call writes open_gate_start[b], the absolute start of the
+ *           gate open after the chunk, or -1.
+ *   final   != 0 changes nothing in the outputs; the state is a fresh stream again after the call.
+ *   Tc      1 .. ofs_rtl_chunk_max_samples(n_br, Q) = 2^21 / n_br - 3Q ((Tc + 3Q) * n_br <= 2^21 keeps
+ *           every prefix an exact integer below 2^53); Tc = 0 with final != 0 is a flush: no samples,
+ *           n_events = 0, open_gate_start as carried, the streams fresh afterwards (x and the arrays
+ *           unused).
+ * EQUIVALENCE GUARANTEE.  For any split of a stream into chunks within the per-call limit, the
+ * concatenated arrays and the concatenated events equal bit for bit what ONE ofs_minn_rtl call on the
+ * whole stream returns, on every input that call handles exactly (its integer-exact plan,
+ * ofs_rtl_plan 2000-2999), and the last call's open_gate_start equals the one-shot call's.  Streams
+ * may be longer than that plan reaches; there the results equal the reference's float64 models.
+ * Calls are stream-ordered and never synchronise with the host: consecutive chunks may be enqueued
+ * back to back.  OFS_EINVAL (before any launch): another in_fmt, n_br outside 1-2, a Q outside the
+ * table, Tc < 0 or above the limit, Tc = 0 without final, B < 0, a null or misaligned state with
+ * B > 0, a null x with B * Tc > 0, smooth_shift or threshold_frac_bits outside 0-62, smooth_mode not 0
+ * or 1, hysteresis < 0 or > OFS_RTL_CHUNK_MAX_HYSTERESIS, max_events < 0, detect with a null n_events
+ * or open_gate_start or with null events while max_events > 0.  There is no fall-back to the general
+ * engine.  ofs_rtl_chunk_state_bytes returns the bytes of ONE stream's state (a multiple of 16) and
+ * ofs_rtl_chunk_max_samples the largest Tc of one call; both return OFS_EINVAL (< 0) for an unsupported
+ * n_br or Q.
+ */
+#define OFS_RTL_CHUNK_MAX_HYSTERESIS (1 << 28)
+int64_t ofs_rtl_chunk_state_bytes(int32_t n_br, int32_t Q);
+int64_t ofs_rtl_chunk_max_samples(int32_t n_br, int32_t Q);
+int32_t ofs_minn_rtl_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t Tc, int32_t Q,
+                           int32_t smooth_shift, int32_t smooth_mode, int64_t threshold_value,
+                           int32_t threshold_frac_bits, void* state,
+                           double* corr_total, double* corr_positive, double* smooth_metric, double* energy_total,
+                           double* corr_scaled, double* energy_scaled, uint8_t* metric_valid, uint8_t* above_threshold,
+                           int32_t detect, int32_t hysteresis, int32_t timing_offset, int32_t max_events,
+                           int32_t* n_events, int64_t* events, int64_t* open_gate_start, int32_t final, void* stream);
+
+/*
  * Gate / peak FSM alone on precomputed metric arrays: replaces minn_rtl.detect_minn_rtl
  * (minn_rtl.py:750-825) when called on an existing MinnRTLMetricState.
  *   corr_positive: [B][T] f64; above_threshold, metric_valid: [B][T] uint8 (0/1);

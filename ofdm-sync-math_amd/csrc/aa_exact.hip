@@ -19,6 +19,7 @@
 #include "ofs_common.h"
 #include "aa_gate.h"
 #include "aa_words.h"
+#include "rtl_smooth.h"
 #include "ofdmsync.h"
 
 using namespace ofs;
@@ -44,21 +45,6 @@ constexpr int XA = OFS_XA_WG;           // aa_exact_kernel workgroup (tuning bui
 #define OFS_XA_WG_I1 64
 #endif
 constexpr int xa_wg(int fmt, int mr, int na) { return (fmt != OFS_C128 && mr == 1 && na == 1) ? OFS_XA_WG_I1 : XA; }
-
-// The same row prefix on int32 values (integer-valued products of 12-bit words: a row of 64·E
-// samples of one or two branches stays below 2^31), exactly the doubles' values
-template <int E>
-struct RowPrefixI {
-    int f[E], excl, tot;
-    __device__ __forceinline__ void run(const int (&v)[E]) {
-        f[0] = v[0];
-#pragma unroll
-        for (int e = 1; e < E; ++e) f[e] = f[e - 1] + v[e];
-        const int incl = scan_add_i32(f[E - 1]);
-        excl = dppz_i<0x138>(incl);                   // wave_shr:1, lane 0 <- 0
-        tot = __builtin_amdgcn_readlane(incl, 63);
-    }
-};
 
 // ------------------------------------------------------------------------------------------
 // sync_aa, integer input (FMT = OFS_CI16, exact) or complex128 (OFS_C128, any T: stream-wide fp64
@@ -216,80 +202,7 @@ struct RtlExactArgs {
     int32_t detect, hyst, toff, max_ev; int32_t* n_ev; int64_t* ev; int64_t* open_start;
 };
 
-// ---- segment-parallel smoothing -----------------------------------------------------------
-// The stream is cut into segments of SEG = 64·SC samples; lane j owns the chunk of SC samples
-// [s0 + SC·j, s0 + SC·(j+1)).  The float IIR s <- s + (c - s)·2^-k (minn_rtl.py:706-715) is
-// evaluated EXACTLY - the reference's sequential operation sequence, contraction off - by
-// every lane over its own chunk, from an entering state that is made self-consistent:
-//   1. guess: each lane maps its chunk from s = 0 and records the affine map s_out = A·s_in + Z;
-//      a wave scan of the maps applied to the exact carried state gives every chunk's
-//      entering state to a few ulps;
-//   2. round: every lane runs the exact recursion over its chunk from its entering state; the
-//      chain is consistent when each lane's entering state equals lane j-1's leaving state
-//      bit for bit (lane 0 enters with the exact carried state).  Otherwise every lane takes
-//      lane j-1's leaving state as its new entering state and the round repeats.
-// The recursion is deterministic, so a consistent chain IS the reference's trajectory (by
-// induction from lane 0).  After round r lanes 0..r are exact, so it ends within 64 rounds
-// (the sequential cost); in practice the guessed trajectories coincide with the exact one
-// inside a chunk or two and a segment takes a few rounds.  The integer floor-shift RTL mode
-// (not contractive to the bit) runs in a walker lane per stream instead (rtl_walk).
-#ifndef OFS_RTL_SC
-#define OFS_RTL_SC 4
-#endif
-constexpr int SC = OFS_RTL_SC;
-static_assert(SC % 2 == 0, "chunk stores go out as 16-byte pairs");
-constexpr int SEG = 64 * SC;
-constexpr int SEG_PAD = SEG + SEG / SC;                // chunk stride SC + 1 doubles (banks)
-__device__ __forceinline__ int seg_at(int i) { return i + i / SC; }
-
-// per-wave LDS: prefix rows k-3MW..k of Ae and Ac, the raw words of rows k-MW..k-1 of every
-// branch (lane-private columns), the segment's corr_positive and energy_scaled
-__host__ __device__ constexpr int rtl_ring_rows(int MW) { return 3 * MW + 1; }
-__host__ __device__ constexpr size_t rtl_wave_lds(int E, int MW, int nb) {
-    return (size_t)2 * rtl_ring_rows(MW) * E * 64 * sizeof(double) + (size_t)2 * SEG_PAD * sizeof(double) +
-           (size_t)nb * MW * E * 64 * sizeof(int32_t);
-}
-
-__device__ __forceinline__ bool same_bits(double a, double b) {
-    return __double_as_longlong(a) == __double_as_longlong(b);
-}
-
-// One walker lane's pass over a segment (phase B below): the reference's IIR (minn_rtl.py:706-715)
-// exactly as written, branch-free per sample, SM = 0 float s += (c - s)/2^k, 1 shift 0 (s = c),
-// 2 RTL floor shift; the threshold decision (:717-722) goes into the stored value's sign bit.
-template <int SM>
-__device__ __forceinline__ void rtl_walk(const double* __restrict__ wcp, double* __restrict__ wes, int n, int v0,
-                                         double inv, double scale, int shift, double& sv, long long& siv) {
-    constexpr long long SIGN = (long long)(1ull << 63);
-    auto step = [&](double c, double es) -> double {
-        if constexpr (SM == 0) sv = sv + (c - sv) * inv;
-        else if constexpr (SM == 1) sv = c;
-        else {
-            const long long ci = (long long)c;
-            siv = shift == 0 ? ci : siv + ((ci - siv) >> shift);
-            sv = (double)siv;
-        }
-        return __longlong_as_double(__double_as_longlong(sv) | (sv * scale >= es ? SIGN : 0ll));
-    };
-    int li = 0;
-    for (; li < v0; ++li) wes[seg_at(li)] = sv;                  // before metric_valid: state held
-    for (; li + 8 <= n; li += 8) {
-        double cb[8], eb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { cb[u] = wcp[seg_at(li + u)]; eb[u] = wes[seg_at(li + u)]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) wes[seg_at(li + u)] = step(cb[u], eb[u]);
-    }
-    for (; li < n; ++li) wes[seg_at(li)] = step(wcp[seg_at(li)], wes[seg_at(li)]);
-}
-
-// workgroup barrier ordering LDS only: a __syncthreads() fence would also wait for every global
-// store in flight (vmcnt(0)), a store round trip per segment
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
+// segment-parallel smoothing, walker lane, LDS layout: rtl_smooth.h (shared with rtl_chunk.hip)
 
 template <int E, int MW, int CPNA, int NBM>
 __global__ __launch_bounds__(XW) void rtl_exact_kernel(RtlExactArgs a) {

@@ -34,7 +34,10 @@ constexpr int ABS_NOKEY = 0x7fffffff;    // absolute sample indices
 // takes the machine's wave-uniform fields from the previous call (absolute indices), save() gives
 // them back, and emit() writes absolute indices.  The start and the peak of a gate that was already
 // open at load() may lie any distance back, so they stay absolute (ev0_abs, b0_abs) behind the
-// CARRIED mark.  The other forms never touch these members.
+// CARRIED mark.  The other forms never touch these members.  Both machines have the form: the
+// minn_rtl one (rtl_chunk.hip) carries the last above position, gate_open, the gate's start, its peak
+// so far and that peak's corr_positive (bpm); its merge() keeps the LAST maximum (>=), so a later
+// equal value of a later call replaces the carried peak.
 template <bool ABS> struct AaGateAbs {};                   // the other forms carry no extra member
 template <> struct AaGateAbs<true> { int64_t abs0, ev0_abs, b0_abs; };
 
@@ -65,8 +68,13 @@ struct AaRowGate : AaGateAbs<ABS> {
         if (evi && n_ev < max_ev && lane < 8) {
             int64_t* ei = evi + (int64_t)n_ev * 4;
             if constexpr (RTL) {
-                const int64_t f[4] = {bidx, (int64_t)bidx + toff, ev_start, (int64_t)gate_end + 1};
-                if (lane < 4) ei[lane] = f[lane & 3];
+                if constexpr (ABS) {
+                    const int64_t f[4] = {out_peak(), out_peak() + toff, out_start(), out_pos(gate_end) + 1};
+                    if (lane < 4) ei[lane] = f[lane & 3];
+                } else {
+                    const int64_t f[4] = {bidx, (int64_t)bidx + toff, ev_start, (int64_t)gate_end + 1};
+                    if (lane < 4) ei[lane] = f[lane & 3];
+                }
             } else {
                 double* er = evr + (int64_t)n_ev * 4;
                 const int64_t f[4] = {out_peak(), out_start(), out_pos(gate_end), out_peak() - 2 * L + 1};
@@ -268,10 +276,10 @@ struct AaRowGate : AaGateAbs<ABS> {
     // after init(): the state an earlier call saved.  carry_p1 = 1 + absolute index of the last
     // above-threshold sample, 0 = none; one further back than gate coordinate 0 is more than
     // max(H, 1) before this call's first sample (the caller's choice of abs0) and is "none": its
-    // gate has closed and any above sample opens the next.
+    // gate has closed and any above sample opens the next.  The minn_rtl machine uses bpm alone.
     __device__ __forceinline__ void load(int64_t abs0_, int64_t carry_p1, int open, int64_t ev_start_abs,
                                          int64_t bidx_abs, V bpm_, V bpr_, V bpi_, V bm_) {
-        static_assert(ABS && !RTL, "resumable form of the sync_aa machine");
+        static_assert(ABS, "resumable form of either machine");
         this->abs0 = abs0_; this->ev0_abs = ev_start_abs; this->b0_abs = bidx_abs;
         const int64_t cg = carry_p1 - 1 - abs0_;
         carry_last = (carry_p1 > 0 && cg >= 0) ? (int)cg : -1;
@@ -282,7 +290,7 @@ struct AaRowGate : AaGateAbs<ABS> {
     }
     // after the call's last row (and merge() if a gate is open): the fields for the next call
     __device__ __forceinline__ void save(int64_t& carry_p1, int& open, int64_t& ev_start_abs, int64_t& bidx_abs) const {
-        static_assert(ABS && !RTL, "resumable form of the sync_aa machine");
+        static_assert(ABS, "resumable form of either machine");
         carry_p1 = carry_last >= 0 ? out_pos(carry_last) + 1 : 0;
         open = gate_open;
         ev_start_abs = out_start();

@@ -81,6 +81,11 @@ def _declare(lib):
                                    c_int32, c_int32, P, P, P, P]),
         "ofs_minn_rtl_gate": (c_int32, [P, P, P, c_int64, c_int64, c_int32, c_int32, c_int32, P, P,
                                         P, P]),
+        "ofs_rtl_chunk_state_bytes": (c_int64, [c_int32, c_int32]),
+        "ofs_rtl_chunk_max_samples": (c_int64, [c_int32, c_int32]),
+        "ofs_minn_rtl_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                         c_int64, c_int32, P, P, P, P, P, P, P, P, P, c_int32, c_int32,
+                                         c_int32, c_int32, P, P, P, c_int32, P]),
         "ofs_cp_cfo": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, P, c_int32, c_int32,
                                  c_double, P, P, P]),
         "ofs_cp_search": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, P, c_int32, c_int32, c_int32,
