@@ -630,6 +630,73 @@ int32_t ofs_zc_gate(const double* corr_mag, const uint8_t* above_threshold, cons
                     uint8_t* gate_mask, int32_t max_events, int32_t* n_events, int64_t* ev_int,
                     double* ev_peak, void* stream);
 
+/*
+ * Resumable chunked zc_v2 CFAR + gate for magnitude streams of any length (the reference calls
+ * zc_streaming_detection "FPGA-friendly streaming detection", zc_v2.py:300-346 + :374-446; its
+ * sample-by-sample loops are the specification).
+ *
+ * A stream's |corr| is fed in consecutive chunks of Tc samples; ofs_zc_detect_chunk returns the chunk's
+ * CFAR arrays, its gate mask and the gate events that CLOSED among its samples, and keeps what the next
+ * call needs in a caller-owned state buffer on the device.  The library allocates nothing and keeps no
+ * global state.
+ *   corr_mag  f64; row b starts at corr_mag + b * ld_mag (elements), ld_mag >= Tc: a column slice of a
+ *           wider buffer (the matched filter's output, say) is passed in place.  Rows need only 8-byte
+ *           alignment.  Element i of a call is the stream's absolute sample
+ *           n = (samples of earlier calls) + i.  W = max(1, window_size); metric_valid = n >= W.  The
+ *           fill phase is decided PER STREAM on n, not per call: after a reset of some state rows the
+ *           streams of one call are at different n.
+ *   state   [B][ofs_zc_chunk_state_bytes(window_size)] bytes, 16-byte aligned, device memory.  The
+ *           layout is opaque: it holds the running sum acc, the last W magnitudes, the int64 sample
+ *           count and the gate machine (open, gate_start, peak_index, peak_value, last above sample).
+ *           ALL-ZERO BYTES ARE A FRESH STREAM, so any subset of streams is reset with a memset of its
+ *           rows (stream-ordered with the calls).  window_size, thresh_value, thresh_frac_bits,
+ *           min_corr_mag, reference_length and hysteresis must not change between the calls of a
+ *           stream (max_events and which arrays are requested may), and the calls of a stream must be
+ *           ordered (same HIP stream, or synchronised by the caller).  W is 1 .. OFS_ZC_CHUNK_MAX_WINDOW.
+ *   local_sum .. gate_mask  dense [B][Tc], f64 / uint8 as in ofs_zc_detect, EACH nullable (events +
+ *           gate_mask only is the benchmarked mode); the values are those of ofs_zc_detect at the same
+ *           absolute sample.
+ *   events  only the gates that closed among this call's samples, written from slot 0 of every call,
+ *           ABSOLUTE int64 indices: ev_int [B][max_events][4] = peak_index, gate_start, gate_end,
+ *           detected_start = max(0, peak_index - reference_length + 1); ev_peak [B][max_events] the
+ *           peak value.  n_events[b] is exact also above max_events; slots at or beyond
+ *           min(n_events, max_events) are not written.  The peak is the FIRST maximum of corr_mag in
+ *           the gate (strict >, the opening sample is the first candidate), across calls too.  A gate
+ *           still open at the end of the chunk is carried, over any number of calls.
+ *   open_gate_start [B], written by every call: the absolute start of the gate that is open after the
+ *           call's last sample, or -1.  On a final call it names the gate that `final` then closes.
+ *   final   != 0: an open gate closes with gate_end = the stream's sample count, as ofs_zc_detect does
+ *           at n, and emits its event; the state is a fresh stream afterwards.  Tc = 0 with final != 0
+ *           is a flush (no samples; corr_mag and the arrays unused); Tc = 0 without final is OFS_EINVAL.
+ * EQUIVALENCE GUARANTEE.  For any split of a stream into chunks, on ANY float64 input (the running sum
+ * is the reference's literal left-to-right recursion acc = (acc + c[n]) - c[n - W] with acc and the
+ * last W magnitudes carried), the concatenated arrays and the concatenated events equal bit for bit
+ * what ONE ofs_zc_detect call on the whole stream returns, with one exception in gate_mask: the
+ * reference sets gate_mask[gate_start:n] for a gate still open at the end (zc_v2.py:444), which
+ * includes the start sample that a closed gate never gets.  The final call sets it wherever those
+ * samples lie in its own chunk; if gate_start lies in an earlier call, that single sample was already
+ * returned as 0, and the last call's open_gate_start names it.
+ * Calls are stream-ordered and never synchronise with the host: consecutive chunks may be enqueued
+ * back to back.  OFS_EINVAL (before any launch): B < 0 or Tc < 0, Tc = 0 without final, ld_mag < Tc
+ * with B > 1, a window_size above OFS_ZC_CHUNK_MAX_WINDOW, thresh_frac_bits outside 0-62,
+ * hysteresis < 0 or > OFS_ZC_CHUNK_MAX_HYSTERESIS, max_events < 0, a null or misaligned state with
+ * B > 0, a null corr_mag with B * Tc > 0 or one that is not 8-byte aligned, a null n_events or
+ * open_gate_start with B > 0, null event arrays with max_events > 0.  B = 0 is a valid no-op with every
+ * pointer null.  ofs_zc_chunk_state_bytes returns the bytes of ONE stream's state (a multiple of 16),
+ * or OFS_EINVAL (< 0) for a window_size below 0 or above the limit (0 counts as 1).
+ */
+#define OFS_ZC_CHUNK_MAX_WINDOW     (1 << 16)
+#define OFS_ZC_CHUNK_MAX_HYSTERESIS (1 << 28)
+int64_t ofs_zc_chunk_state_bytes(int32_t window_size);
+int32_t ofs_zc_detect_chunk(const double* corr_mag, int64_t ld_mag, int64_t B, int64_t Tc,
+                            int32_t window_size, int64_t thresh_value, int32_t thresh_frac_bits,
+                            double min_corr_mag, int32_t reference_length, int32_t hysteresis,
+                            void* state,
+                            double* local_sum, double* corr_scaled, double* thresh_scaled,
+                            uint8_t* above_threshold, uint8_t* metric_valid, uint8_t* gate_mask,
+                            int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_peak,
+                            int64_t* open_gate_start, int32_t final, void* stream);
+
 /* ---- detection post-processing (metric streams -> timing decisions) -------------------------
  * Metrics are [B][n] device arrays; `precision` names their element type (OFS_FP32 = float,
  * OFS_FP64 = double).  Smoothed outputs are f64.  Per-stream `status` reports what the

@@ -149,6 +149,10 @@ def _declare(lib):
         "ofs_zc_detect_plan": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32]),
         "ofs_zc_gate": (c_int32, [P, P, P, c_int64, c_int64, c_int32, c_int32, P, c_int32, P, P, P,
                                   P]),
+        "ofs_zc_chunk_state_bytes": (c_int64, [c_int32]),
+        "ofs_zc_detect_chunk": (c_int32, [P, c_int64, c_int64, c_int64, c_int32, c_int64, c_int32, c_double,
+                                          c_int32, c_int32, P, P, P, P, P, P, P, c_int32, P, P, P, P,
+                                          c_int32, P]),
         "ofs_debug_set_variant": (c_int32, [ctypes.c_char_p, c_int64]),
         "ofs_debug_get_variant": (c_int64, [ctypes.c_char_p]),
         "ofs_debug_reset_variants": (c_int32, []),

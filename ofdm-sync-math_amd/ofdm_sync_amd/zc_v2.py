@@ -362,14 +362,15 @@ def detect_zc_preamble_batched(x, reference=None, window_size: int = CORR_WINDOW
                                thresh_value: int = THRESH_VALUE, thresh_frac_bits: int = THRESH_FRAC_BITS,
                                min_corr_mag: float = MIN_CORR_MAG, hysteresis: int = HYSTERESIS,
                                normalize: bool = True, max_events: int = 8,
-                               want_state: bool = True) -> ZCBatchResult:
+                               want_state: bool = True, method: str = "auto") -> ZCBatchResult:
     """detect_zc_preamble over x[B, n_branch, T]; everything stays on the device.  ``reference``:
-    taps or a MatchedFilter (default: the PSS symbol of build_pss_symbol)."""
+    taps or a MatchedFilter (default: the PSS symbol of build_pss_symbol).  ``method`` is
+    ``correlate_batched``'s ("auto", "direct" or "fft")."""
     if reference is None:
         reference = build_pss_symbol(include_cp=False)
     ref_len = int(len(reference))
     _, mag = correlate_batched(x, reference, OFS_ZC_V2 if normalize else OFS_ZC_SUM,
-                               want_corr=False, want_mag=True)
+                               want_corr=False, want_mag=True, method=method)
     E = int(max_events)
     while True:
         st, gate, n_ev, ev_i, ev_v = _detect_run(mag, window_size, thresh_value, thresh_frac_bits,
@@ -380,6 +381,200 @@ def detect_zc_preamble_batched(x, reference=None, window_size: int = CORR_WINDOW
         E = worst
     return ZCBatchResult(corr_mag=mag, state=st, gate_mask=gate, n_events=n_ev, events=ev_i,
                          peak_values=ev_v)
+
+
+CHUNK_ARRAYS = (("local_sum", torch.float64), ("corr_scaled", torch.float64), ("thresh_scaled", torch.float64),
+                ("above_threshold", torch.uint8), ("metric_valid", torch.uint8), ("gate_mask", torch.uint8))
+
+
+@dataclass
+class ZCChunkResult:
+    """One call of ZCChunkedDetector: arrays [B, Tc] (None unless requested), n_events [B] (the gates
+    that closed in this call; may exceed max_events), events [B, E, 4] = peak_index, gate_start,
+    gate_end, detected_start (absolute), peak_values [B, E], open_gate_start [B] (-1: none), and for
+    ``push`` corr_mag [B, Tc] (a view of the correlation's output).  ``tail``: after ``push(x, final=True)``
+    the result of the ``flush()`` that followed, else None."""
+    local_sum: torch.Tensor | None
+    corr_scaled: torch.Tensor | None
+    thresh_scaled: torch.Tensor | None
+    above_threshold: torch.Tensor | None
+    metric_valid: torch.Tensor | None
+    gate_mask: torch.Tensor | None
+    n_events: torch.Tensor
+    events: torch.Tensor
+    peak_values: torch.Tensor
+    open_gate_start: torch.Tensor
+    corr_mag: torch.Tensor | None = None
+    tail: "ZCChunkResult | None" = None
+
+
+class ZCChunkedDetector:
+    """Resumable zc_v2 detection over B streams that arrive in chunks (``ofs_zc_detect_chunk``).
+
+    ``push_mag(corr_mag)`` takes the next ``Tc`` magnitudes of every stream, ``push(x)`` the next
+    ``Tc`` samples ``[B, n_branch, Tc]`` (any format ``detect_zc_preamble_batched`` takes) and runs
+    the matched filter in front.  Both return the CFAR arrays asked for in ``outputs``, the gate mask
+    and the events of the gates that CLOSED among those samples, with ABSOLUTE indices; a gate still
+    open at the end of a chunk is carried into the next call and named by ``open_gate_start``.  For any
+    chunking, on any float64 magnitudes, the concatenated arrays and events equal the one-shot
+    ``ofs_zc_detect`` / ``detect_zc_preamble_batched`` (direct correlation) on the whole stream bit for
+    bit - the running sum is the reference's literal recursion with its state carried - with ONE
+    exception in ``gate_mask``: for a gate still open at the very end the reference also marks the
+    gate's start sample (zc_v2.py:444); the final call does so where that sample lies in its own chunk,
+    and otherwise the sample was already returned as 0 (``open_gate_start`` of the last call names it).
+
+    ``push(x, final=True)`` = ``push(x)`` followed by ``flush()``; it returns the chunk's result like any
+    push, with the flush's result in its ``tail``.
+    ``flush()`` feeds the ``N - 1`` zero samples of the convolution tail (outputs ``T .. T + N - 2``),
+    closes open gates at ``T + N - 1`` as the one-shot call does, and leaves fresh streams behind.
+    ``reset(mask)`` makes the masked streams fresh without closing anything.
+
+    COST OF ``push``.  The matched filter is the direct kernel: ``O(N)`` multiply-adds per output, and
+    every push recomputes ``2 (N - 1)`` outputs it does not use (the head of ``[history | x]`` and its
+    tail), so chunks should be several reference lengths long.  A chunked FFT overlap-save front end is
+    out of scope: its rounding depends on where a sample sits in its block, so it could not give the
+    bit-for-bit guarantee.
+
+    The per-stream state lives on the device in ``self.state`` (and the last ``N - 1`` samples in
+    ``self.history``); a push enqueues its launches on the current stream and never synchronises.  An
+    event overflow is visible as ``n_events > max_events``: size ``max_events`` for the busiest chunk
+    (``max_events=0``: no event arrays are written, only counts, mask and ``open_gate_start``).
+    THE RESULT BUFFERS ARE THE DETECTOR'S: they are cached per kind of call and ``Tc`` and a later push of the same
+    length overwrites them (in stream order) - clone what must outlive it.  Event slots at or beyond
+    ``n_events[b]`` are not written by a call.  The parameters are fixed for the detector's life.
+    """
+
+    def __init__(self, B: int, reference=None, n_branch: int = 1, *, window_size: int = CORR_WINDOW_SIZE,
+                 thresh_value: int = THRESH_VALUE, thresh_frac_bits: int = THRESH_FRAC_BITS,
+                 min_corr_mag: float = MIN_CORR_MAG, hysteresis: int = HYSTERESIS, normalize: bool = True,
+                 outputs=("gate_mask",), max_events: int = 8, device=None):
+        dev = torch.device(device) if device is not None else _lib.require_gpu()
+        lib = _lib.lib()
+        nbytes = int(lib.ofs_zc_chunk_state_bytes(int(window_size)))
+        if nbytes < 0 or B < 0 or n_branch < 1:
+            raise ValueError(f"ZCChunkedDetector: window_size 0 .. 65536, B >= 0, n_branch >= 1 "
+                             f"(got window_size={window_size}, B={B}, n_branch={n_branch})")
+        names = [k for k, _ in CHUNK_ARRAYS]
+        bad = [k for k in outputs if k not in names]
+        if bad:
+            raise ValueError(f"outputs must be among {names}, got {bad}")
+        if reference is None:
+            reference = build_pss_symbol(include_cp=False)
+        self.mf = reference if isinstance(reference, MatchedFilter) else MatchedFilter(reference, dev)
+        self.N = len(self.mf)
+        self.B, self.n_branch, self.device = int(B), int(n_branch), dev
+        self.mode = OFS_ZC_V2 if normalize else OFS_ZC_SUM
+        self.outputs = tuple(outputs)
+        if int(max_events) < 0:
+            raise ValueError(f"max_events must be >= 0, got {max_events}")
+        self.max_events = int(max_events)          # 0: counts, mask and open_gate_start only (no event arrays)
+        self._par = (int(window_size), int(thresh_value), int(thresh_frac_bits), float(min_corr_mag),
+                     self.N, int(hysteresis))
+        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)      # all-zero = fresh
+        self.history = None            # [B, n_branch, N - 1] samples, in the format of the first push
+        self._fn = lib.ofs_zc_detect_chunk
+        self._bufs: dict = {}
+
+    def _buffers(self, kind: str, Tc: int) -> ZCChunkResult:
+        """The cached result of (kind of call, Tc): the shape is part of the key, so a Tc = 0 flush and a
+        tail flush, or a push and a push_mag of one length, never share buffers."""
+        key = (kind, Tc)
+        r = self._bufs.get(key)
+        if r is None:
+            B, dev, E = self.B, self.device, max(self.max_events, 1)
+            arr = {k: (torch.zeros((B, Tc), dtype=dt, device=dev) if k in self.outputs and Tc else None)
+                   for k, dt in CHUNK_ARRAYS}
+            r = self._bufs[key] = ZCChunkResult(
+                **arr, n_events=torch.zeros((B,), dtype=torch.int32, device=dev),
+                events=torch.zeros((B, E, 4), dtype=torch.int64, device=dev),
+                peak_values=torch.zeros((B, E), dtype=torch.float64, device=dev),
+                open_gate_start=torch.full((B,), -1, dtype=torch.int64, device=dev))
+        return r
+
+    def _call(self, mag, ld: int, Tc: int, final: bool, kind: str) -> ZCChunkResult:
+        r = self._buffers(kind, Tc)
+        rc = self._fn(_lib.ptr(mag), int(ld), self.B, Tc, *self._par, self.state.data_ptr(),
+                      _lib.ptr(r.local_sum), _lib.ptr(r.corr_scaled), _lib.ptr(r.thresh_scaled),
+                      _lib.ptr(r.above_threshold), _lib.ptr(r.metric_valid), _lib.ptr(r.gate_mask),
+                      self.max_events, r.n_events.data_ptr(), r.events.data_ptr() if self.max_events else None,
+                      r.peak_values.data_ptr() if self.max_events else None,
+                      r.open_gate_start.data_ptr(), int(bool(final)), _lib.stream_ptr())
+        _lib.check(rc, "ofs_zc_detect_chunk")
+        return r
+
+    def push_mag(self, corr_mag: torch.Tensor, final: bool = False, _kind: str = "mag") -> ZCChunkResult:
+        """The next ``Tc`` magnitudes ``[B, Tc]`` float64 of every stream in ONE ofs_zc_detect_chunk call.
+        A column slice of a wider buffer is taken in place (its row stride is passed as ``ld_mag``);
+        ``final=True`` also ends the streams (open gates close at the sample count)."""
+        if corr_mag.dim() != 2 or corr_mag.shape[0] != self.B or corr_mag.dtype != torch.float64:
+            raise ValueError(f"corr_mag must be [{self.B}, Tc] float64, got {tuple(corr_mag.shape)} {corr_mag.dtype}")
+        Tc = int(corr_mag.shape[1])
+        if Tc == 0 and not final:
+            raise ValueError("an empty chunk is only valid with final=True")
+        if corr_mag.device != self.device:
+            corr_mag = corr_mag.to(self.device)
+        if Tc > 1 and corr_mag.stride(1) != 1 or (self.B > 1 and corr_mag.stride(0) < Tc):
+            corr_mag = corr_mag.contiguous()
+        ld = corr_mag.stride(0) if self.B > 1 else max(Tc, 1)
+        return self._call(corr_mag if Tc and self.B else None, ld, Tc, final, _kind)
+
+    def _samples(self, x):
+        """x as a device tensor [B, n_branch, Tc] (+ a trailing I/Q axis for int16)."""
+        batch = _lib.as_batch(x, batched=True)
+        if batch.fmt == _lib.CP12 or batch.B != self.B or batch.nb != self.n_branch:
+            raise ValueError(f"chunk must be [{self.B}, {self.n_branch}, Tc] complex or int16 I/Q samples")
+        tail = (2,) if batch.fmt == _lib.CI16 else ()
+        return batch.data.reshape((self.B, self.n_branch, batch.T) + tail)
+
+    def _push(self, d: torch.Tensor, final: bool, kind: str) -> ZCChunkResult:
+        N, Tc = self.N, int(d.shape[2])
+        if self.history is None:
+            self.history = torch.zeros((self.B, self.n_branch, N - 1) + tuple(d.shape[3:]), dtype=d.dtype,
+                                       device=self.device)
+        if d.dtype != self.history.dtype:
+            raise ValueError(f"chunks of one stream must keep their sample format ({self.history.dtype}, got {d.dtype})")
+        cat = torch.cat((self.history, d), dim=2)
+        # output k of [history | x] is the stream's absolute output n0 - (N - 1) + k
+        _, mag = correlate_batched(cat, self.mf, self.mode, want_corr=False, want_mag=True, method="direct")
+        cols = mag[:, N - 1:N - 1 + Tc]
+        r = self.push_mag(cols, final, kind)
+        r.corr_mag, r.tail = cols, None
+        self.history = cat[:, :, Tc:].contiguous()
+        return r
+
+    def push(self, x, final: bool = False):
+        """The next ``Tc >= 1`` samples of every stream.  ``final=True``: then ``flush()``, whose result is
+        the returned result's ``tail``."""
+        d = self._samples(x)
+        if d.shape[2] == 0:
+            raise ValueError("push needs at least one sample; flush() ends the streams")
+        r = self._push(d, False, "push")
+        if final:
+            r.tail = self.flush()
+        return r
+
+    def flush(self) -> ZCChunkResult:
+        """End the streams: the ``N - 1`` outputs of the convolution tail, open gates close at
+        ``T + N - 1`` and emit; the streams are fresh afterwards (and may continue in another sample
+        format).  Before any push there is no tail: the call only closes what ``push_mag`` left open."""
+        if self.N == 1 or self.B == 0 or self.history is None:
+            r = self._call(None, 1, 0, True, "flush")
+        else:
+            r = self._push(torch.zeros_like(self.history), True, "flush")
+        self.history = None
+        return r
+
+    def reset(self, mask: torch.Tensor | None = None) -> None:
+        """Make all streams fresh, or those where ``mask`` [B] (bool) is set, without closing their
+        gates (stream-ordered, no synchronisation)."""
+        if mask is None:
+            self.state.zero_()
+            self.history = None
+        else:
+            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
+            self.state.masked_fill_(m[:, None], 0)
+            if self.history is not None:
+                self.history.masked_fill_(m.reshape((-1,) + (1,) * (self.history.dim() - 1)), 0)
 
 
 def detect_zc_preamble(rx_samples, window_size: int = CORR_WINDOW_SIZE, thresh_value: int = THRESH_VALUE,
