@@ -26,44 +26,11 @@
 // still open at the end.  Shorter hysteresis runs the sequential kernel of corr.hip.
 #include "ofs_common.h"
 #include "ofdmsync.h"
+#include "zc_tiles.h"
 
 using namespace ofs;
 
 namespace {
-
-// streams per workgroup (walker lanes) and helper waves: LDS-DMA path 16 streams, 11 helpers (one
-// workgroup of 12 waves per CU, 154 VGPRs = 3 waves/SIMD; round 5, paired builds on zc_detect: 7 / 8 /
-// 11 / 15 helpers 0.306 / 0.289 / 0.286 / 0.492 ms, profiles/r05p_zc_cfar_helpers_ab.txt; static LDS (4 + 3 + 2) x 16 x 130 doubles = 149,760 B = 146.25 KiB of
-// gfx950's 160 KiB, asserted in the kernel); register path 8 streams, 3 helpers ((3 + 2 + 2) x 8 x
-// 130 doubles = 57 KiB; its staging registers scale with the stream count)
-#ifndef OFS_ZC_S
-#define OFS_ZC_S 16
-#endif
-#ifndef OFS_ZC_H
-#define OFS_ZC_H 11
-#endif
-#ifndef OFS_ZC_S_REG
-#define OFS_ZC_S_REG 8
-#endif
-#ifndef OFS_ZC_H_REG
-#define OFS_ZC_H_REG 3
-#endif
-#ifndef OFS_ZC_R
-#define OFS_ZC_R 2
-#endif
-// diagnostic builds: OFS_ZC_NOWALK / OFS_ZC_NOHELP skip the walker / the helpers (timing only)
-#ifndef OFS_ZC_NOWALK
-#define OFS_ZC_NOWALK 0
-#endif
-#ifndef OFS_ZC_NOCHAIN
-#define OFS_ZC_NOCHAIN 0
-#endif
-#ifndef OFS_ZC_NOHELP
-#define OFS_ZC_NOHELP 0
-#endif
-constexpr int ZR = OFS_ZC_R;      // 64-sample rows of the gate machine per chunk
-constexpr int ZC = 64 * ZR;       // samples per chunk
-constexpr int ZP = ZC + 2;        // LDS row pitch in doubles (16-byte rows; walker column reads spread over banks)
 
 struct ZcArgs {
     const double* mag;
@@ -74,18 +41,13 @@ struct ZcArgs {
     int max_ev; int32_t* n_ev; int64_t* ev; double* ev_v;
 };
 
-// per-stream gate state, wave-uniform in the helper wave that owns the stream
-struct ZGate {
-    int64_t last_above;     // last above sample (< current row), -1 if none
-    int64_t gs, pk;
-    double pv;
-    int open, nev;
-};
-
 // DMA: the walker stages the c / c[i-W] tiles with LDS-DMA (global_load_lds_dwordx4, no
 // registers), two chunks ahead of use instead of one (the register path's loads land one chunk
 // period after they are issued, so a chunk could not be shorter than a memory round trip);
 // taken when every tile row is a whole, 16-byte-aligned 1 KiB span (host checks).
+// HG: the helpers read c from global memory (L2: the walker's DMA brought the rows in) instead of the
+// LDS tile: taken when state arrays are stored (paired, r06k: state mode 0.564 -> 0.540 ms;
+// events + mask only 0.285 -> 0.342 ms, so not there)
 
 #ifndef OFS_ZC_TIMING
 #define OFS_ZC_TIMING 0            // diagnostic builds: per-role cycles (tools/zc_phase.py)
@@ -98,94 +60,6 @@ __device__ unsigned zc_hwid[4096 * 8];       // HW_ID of every wave (workgroup-m
 #else
 #define ZC_T(i)
 #endif
-#ifndef OFS_ZC_ZB
-#define OFS_ZC_ZB 8                // walker: samples per LDS batch (read one batch ahead of the adds)
-#endif
-#ifndef OFS_ZC_DIAG_NOLDS
-#define OFS_ZC_DIAG_NOLDS 0        // diagnostic builds (timing only, wrong results): helpers read no LDS
-#endif
-#ifndef OFS_ZC_DIAG_NOST
-#define OFS_ZC_DIAG_NOST 0         // ... helpers store nothing on quiet chunks
-#endif
-#ifndef OFS_ZC_WUNROLL
-#define OFS_ZC_WUNROLL 16          // walker: LDS batches unrolled per chunk (code size A/B)
-#endif
-#ifndef OFS_ZC_HUNROLL
-#define OFS_ZC_HUNROLL 2           // helpers: rows of the gate pass unrolled (code size A/B)
-#endif
-#ifndef OFS_ZC_ISOLATE
-#define OFS_ZC_ISOLATE 0           // 1: the walker's SIMD-mates idle (A/B, r05ao: bit-identical, 0.2925 vs
-                                   // 0.2864 ms with 9 working helpers; 13 waves 0.444 - SIMD sharing is
-                                   // not what slows the walker's chain, as round 3 found by other means)
-#endif
-#ifndef OFS_ZC_QUIET
-#define OFS_ZC_QUIET 1             // 0: gate machine on every row (A/B)
-#endif
-// state / mask stores of the helpers: non-temporal (streamed past the caches; nothing here reads
-// them back).  r05av, bit-identical: state arrays 0.63 -> 0.56 ms, events + mask unchanged (0.286)
-#ifndef OFS_ZC_NT
-#define OFS_ZC_NT 1
-#endif
-// helpers read c from global memory (L2: the walker's DMA brought the rows in) instead of the LDS
-// tile, template HG: taken when state arrays are stored (paired, r06k: state mode 0.564 -> 0.540 ms;
-// events + mask only 0.285 -> 0.342 ms, so not there); OFS_ZC_HGLOBAL = 1 forces it (A/B)
-#ifndef OFS_ZC_HGLOBAL
-#define OFS_ZC_HGLOBAL 0
-#endif
-template <class T>
-__device__ __forceinline__ void zc_st(T* p, T v) {
-#if OFS_ZC_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-
-// walker: the exact left-to-right recursion of RunningSum.step over one full chunk of this lane's
-// stream; LDS reads a batch ahead of the dependent adds (the chain is 2 v_add_f64 per sample; an
-// LDS round trip per sample would set the pace instead).  OZ: c[i-W] is 0 (window not yet full).
-template <int ZCN, bool OZ>
-__device__ __forceinline__ void zc_walk_chunk(const double* x, const double* o, double* r, double& acc) {
-#pragma clang fp contract(off)
-    constexpr int ZB = OFS_ZC_ZB;
-    double2 xv[ZB / 2], ov[ZB / 2];
-#pragma unroll
-    for (int j = 0; j < ZB / 2; ++j) {
-        xv[j] = reinterpret_cast<const double2*>(x)[j];
-        if (!OZ) ov[j] = reinterpret_cast<const double2*>(o)[j];
-    }
-#pragma unroll OFS_ZC_WUNROLL
-    for (int bb = 0; bb < ZCN / ZB; ++bb) {
-        double2 xn[ZB / 2], on[ZB / 2];
-        if (bb + 1 < ZCN / ZB) {
-#pragma unroll
-            for (int j = 0; j < ZB / 2; ++j) {
-                xn[j] = reinterpret_cast<const double2*>(x + (bb + 1) * ZB)[j];
-                if (!OZ) on[j] = reinterpret_cast<const double2*>(o + (bb + 1) * ZB)[j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < ZB / 2; ++j) {
-            double2 rr;
-#if OFS_ZC_NOCHAIN
-            rr.x = xv[j].x - (OZ ? 0.0 : ov[j].x); rr.y = xv[j].y - (OZ ? 0.0 : ov[j].y);
-#else
-            if (OZ) {
-                acc = acc + xv[j].x; rr.x = acc;
-                acc = acc + xv[j].y; rr.y = acc;
-            } else {
-                acc = (acc + xv[j].x) - ov[j].x; rr.x = acc;
-                acc = (acc + xv[j].y) - ov[j].y; rr.y = acc;
-            }
-#endif
-            reinterpret_cast<double2*>(r + bb * ZB)[j] = rr;
-        }
-        if (bb + 1 < ZCN / ZB) {
-#pragma unroll
-            for (int j = 0; j < ZB / 2; ++j) { xv[j] = xn[j]; if (!OZ) ov[j] = on[j]; }
-        }
-    }
-}
 
 template <bool DMA, int ZS, int ZH, bool HG>
 __global__ __launch_bounds__(64 * (1 + ZH))
@@ -203,29 +77,25 @@ void zc_cfar_kernel(ZcArgs a) {
     __shared__ double to[NO][ZS][ZP];     // c[i - W] (0 before the window fills)
     __shared__ double ta[2][ZS][ZP];      // running sum after sample i
     static_assert(sizeof(tc) + sizeof(to) + sizeof(ta) <= 160 * 1024,
-                  "zc_cfar_kernel: static LDS beyond gfx950's 160 KiB per workgroup (OFS_ZC_S / ZC / ZP)");
+                  "zc_cfar_kernel: static LDS beyond gfx950's 160 KiB per workgroup (ZS / ZC / ZP)");
     const int lane = threadIdx.x & 63;
     // role of this wave: 0 = walker, 1..ZH = helpers.  (Measured and not kept: the walker chosen by
     // SIMD id so both workgroups' walkers share a SIMD, 0.38 -> 0.45 ms; an idle 8th wave as the
-    // walker's SIMD partner, 0.362 -> 0.373 ms: SIMD sharing is not what slows the chain.)
+    // walker's SIMD partner, 0.362 -> 0.373 ms; the walker's SIMD-mates, waves 4, 8, ... of the
+    // workgroup, idling at the barriers only, r05ao: bit-identical, 0.2925 vs 0.2864 ms with 9 working
+    // helpers, 13 waves 0.444: SIMD sharing is not what slows the chain.)
     const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    // OFS_ZC_ISOLATE: a workgroup's waves go to the CU's SIMDs in a fixed cyclic order (wave w shares
-    // the SIMD of wave w mod 4), so waves 4, 8, ... would share the walker's SIMD and take issue
-    // slots from its dependent chain; they idle (barriers only) and the other waves are the helpers
-    constexpr int ZHE = OFS_ZC_ISOLATE ? ZH - ZH / 4 : ZH;            // helper waves doing work
-    constexpr int NJ = (ZS + ZHE - 1) / ZHE;                         // streams per helper wave
-    const bool idle_w = OFS_ZC_ISOLATE && wv > 0 && (wv & 3) == 0;
-    const int hi = OFS_ZC_ISOLATE ? wv - 1 - (wv >> 2) : wv - 1;     // helper rank (valid if !idle_w)
+    constexpr int NJ = (ZS + ZH - 1) / ZH;                           // streams per helper wave
+    const int hi = wv - 1;                                           // helper rank
     const int64_t b0 = (int64_t)blockIdx.x * ZS;
     const int ns = (int)min((int64_t)ZS, a.B - b0);          // streams of this workgroup
     const int64_t n = a.n;
     const int nch = (int)((n + ZC - 1) / ZC);
 
     // loader = the walker wave, which issues no global stores: its wait for the loads of the next
-    // chunk (staged one iteration after they are issued) never drains the helpers' stores
-    // loader = the walker wave, which issues no global stores: its wait for the loads of the next
     // chunk (staged one iteration after they are issued) never drains the helpers' stores.
     // (Two register sets, loads two chunks ahead: measured slower, 0.64 vs 0.46 ms.)
+    // zc_chunk_kernel has its own load / stage pair: its c[i-W] comes from the carried history ring.
     double pc[ZR][ZS], po[ZR][ZS];
     const double* cw = a.mag + b0 * n;                        // this workgroup's streams
     auto load = [&](int q) {
@@ -266,14 +136,12 @@ void zc_cfar_kernel(ZcArgs a) {
         }
     };
 
-    ZGate g[NJ];
+    ZcGate g[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) { g[j].last_above = -1; g[j].gs = 0; g[j].pk = 0; g[j].pv = 0.0; g[j].open = 0; g[j].nev = 0; }
     double acc = 0.0;                                         // walker lane s < ns: stream b0 + s
 
-    // LDS-only barrier: the helpers' global stores are never waited for (a __syncthreads() fence
-    // would drain them, a full store round trip per chunk); the loads are staged one iteration
-    // after they are issued, so their wait overlaps a whole chunk of work
+    // LDS-only barrier (zc_tiles.h): the helpers' global stores are never waited for
     auto lds_barrier = [] {
         if constexpr (DMA) {
             // no memory-model fence here: with LDS-DMA in the kernel the compiler implements a
@@ -284,9 +152,7 @@ void zc_cfar_kernel(ZcArgs a) {
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         } else {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            zc_lds_barrier();
         }
     };
     if (wv == 0) {
@@ -321,7 +187,7 @@ void zc_cfar_kernel(ZcArgs a) {
         }
         if (wv == 0) {
             // ---- walker: the exact left-to-right recursion of RunningSum.step ----
-            if (!OFS_ZC_NOWALK && q < nch && lane < ZS) {
+            if (q < nch && lane < ZS) {
                 const int cnt = (int)min((int64_t)ZC, n - (int64_t)q * ZC);
                 const double* x = tc[q % NC][lane];
                 const double* o = to[q % NO][lane];
@@ -337,34 +203,34 @@ void zc_cfar_kernel(ZcArgs a) {
                 }
             }
             ZC_T(1)
-        } else if (!OFS_ZC_NOHELP && q >= 1 && !idle_w) {
+        } else if (q >= 1) {
             // ---- helpers: chunk q-1 (flags, stores, gate) ----
             const int qc = q - 1;
-            // pass 1 (OFS_ZC_QUIET): the flags of every (row, stream) of this wave.  A chunk with no
+            // pass 1: the flags of every (row, stream) of this wave.  A chunk with no
             // above sample and no open gate (the common case: events are sparse) needs no gate
             // logic - its gate_mask rows are 0 - so the wave skips the scalar gate machine.
-            bool quiet = OFS_ZC_QUIET != 0;
+            bool quiet = true;
             double cv[ZR][NJ], lv[ZR][NJ];
             uint64_t am[ZR][NJ];
             // every LDS read of the chunk first (one latency for all of them, not one per row),
-            // then the flags with non-short-circuit logic (no exec-mask branches per term)
+            // then the flags with non-short-circuit logic (no exec-mask branches per term).
+            // zc_chunk_kernel has these loops too (rotated tile slots, valid from the stream's own
+            // count); the decision itself, zc_above, is shared.  The ballots and the quiet decision
+            // as one template function with the valid test as a lambda: 3999 -> 4001, 3886 -> 3891,
+            // 4981 -> 4985 instructions here, 8572 -> 8573 there, so both stay written out.
 #pragma unroll
             for (int rr = 0; rr < ZR; ++rr)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    const int s = hi + ZHE * j;
+                    const int s = hi + ZH * j;
                     const int sr = s < ns ? s : 0;
-#if OFS_ZC_DIAG_NOLDS                                           // diagnostic: no helper LDS reads
-                    cv[rr][j] = 1e-3 * (double)(lane + sr) + (double)qc; lv[rr][j] = cv[rr][j] * 1e30;
-#else
-                    if constexpr (HG || OFS_ZC_HGLOBAL) {
+                    if constexpr (HG) {
                         const int64_t ig = (int64_t)qc * ZC + 64 * rr + lane;
                         cv[rr][j] = ig < n ? cw[(int64_t)sr * n + ig] : 0.0;
                     } else {
                         cv[rr][j] = tc[qc % NC][sr][64 * rr + lane];
                     }
                     lv[rr][j] = ta[qc & 1][sr][64 * rr + lane];
-#endif
                 }
 #pragma unroll
             for (int rr = 0; rr < ZR; ++rr) {
@@ -372,16 +238,15 @@ void zc_cfar_kernel(ZcArgs a) {
                 const bool vd = (i < n) & (i >= a.W);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    const int s = hi + ZHE * j;
-                    const bool ab = (s < ns) & vd & (cv[rr][j] * a.scale >= lv[rr][j] * a.tv) & (cv[rr][j] >= a.minmag);
-                    am[rr][j] = __ballot(ab);
+                    const int s = hi + ZH * j;
+                    am[rr][j] = zc_above(a, (s < ns) & vd, cv[rr][j], lv[rr][j]);
                     if (am[rr][j]) quiet = false;
                 }
             }
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 if (g[j].open) quiet = false;
-#pragma unroll OFS_ZC_HUNROLL
+#pragma unroll
             for (int rr = 0; rr < ZR; ++rr) {
             const int64_t base = (int64_t)qc * ZC + 64 * rr;
             const int64_t i = base + lane;
@@ -389,7 +254,7 @@ void zc_cfar_kernel(ZcArgs a) {
             const bool vd = inb && i >= a.W;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const int s = hi + ZHE * j;
+                const int s = hi + ZH * j;
                 if (s >= ns) break;
                 const double c = cv[rr][j];
                 const double ls = lv[rr][j];
@@ -398,17 +263,10 @@ void zc_cfar_kernel(ZcArgs a) {
                 const bool ab = (abm >> lane) & 1;
                 const int64_t o = (b0 + s) * n + i;
                 if (quiet) {
-                    if (inb && !OFS_ZC_DIAG_NOST) {
-                        if (a.local_sum) zc_st(&a.local_sum[o], ls);
-                        if (a.corr_scaled) zc_st(&a.corr_scaled[o], cs);
-                        if (a.thresh_scaled) zc_st(&a.thresh_scaled[o], th);
-                        if (a.above) zc_st(&a.above[o], (uint8_t)0);
-                        if (a.valid) zc_st(&a.valid[o], (uint8_t)vd);
-                        if (a.gate_mask) zc_st(&a.gate_mask[o], (uint8_t)0);
-                    }
+                    if (inb) zc_store(a, o, ls, cs, th, 0, vd, 0);
                     continue;
                 }
-                ZGate& G = g[j];
+                ZcGate& G = g[j];
                 // gate in closed form (Hp >= 64): carried close first, then this row's first above
                 int close_l = -1;                                     // row lane of the close
                 if (G.open) {
@@ -423,41 +281,19 @@ void zc_cfar_kernel(ZcArgs a) {
                 const int cend = carried ? (close_l >= 0 ? close_l : 63) : -1;
                 const bool mk = inb && ((lane <= cend) || (opens && lane > open_l));
                 if (carried) {                                       // peak over [0, cend]
-                    const double v = (inb && lane <= cend) ? c : -__builtin_huge_val();
-                    const double m = wave_max(v);
-                    if (m > G.pv) {
-                        const uint64_t at = __ballot(inb && lane <= cend && c == m);
-                        G.pv = m; G.pk = base + __builtin_ctzll(at);
-                    }
+                    zc_peak(G, inb && lane <= cend, c, base);
                     if (close_l >= 0) {
-                        if (a.ev && G.nev < a.max_ev && lane < 4) {
-                            int64_t* r = a.ev + ((b0 + s) * (int64_t)a.max_ev + G.nev) * 4;
-                            const int64_t ds = G.pk - a.reflen + 1 > 0 ? G.pk - a.reflen + 1 : 0;
-                            r[lane] = lane == 0 ? G.pk : lane == 1 ? G.gs : lane == 2 ? base + close_l : ds;
-                            if (lane == 0 && a.ev_v) a.ev_v[(b0 + s) * (int64_t)a.max_ev + G.nev] = G.pv;
-                        }
-                        G.nev += 1; G.open = 0; G.pv = 0.0;
+                        ZC_EVENT(a, G, b0 + s, base + close_l, lane);
+                        G.open = 0; G.pv = 0.0;
                     }
                 }
                 if (opens) {                                         // opening sample, then (open, 63]
                     G.open = 1; G.gs = base + open_l; G.pk = G.gs;
                     G.pv = readlane(c, open_l);
-                    const double v = (inb && lane > open_l) ? c : -__builtin_huge_val();
-                    const double m = wave_max(v);
-                    if (m > G.pv) {
-                        const uint64_t at = __ballot(inb && lane > open_l && c == m);
-                        G.pv = m; G.pk = base + __builtin_ctzll(at);
-                    }
+                    zc_peak(G, inb && lane > open_l, c, base);
                 }
                 if (abm) G.last_above = base + 63 - __builtin_clzll(abm);
-                if (inb) {
-                    if (a.local_sum) zc_st(&a.local_sum[o], ls);
-                    if (a.corr_scaled) zc_st(&a.corr_scaled[o], cs);
-                    if (a.thresh_scaled) zc_st(&a.thresh_scaled[o], th);
-                    if (a.above) zc_st(&a.above[o], (uint8_t)ab);
-                    if (a.valid) zc_st(&a.valid[o], (uint8_t)vd);
-                    if (a.gate_mask) zc_st(&a.gate_mask[o], (uint8_t)mk);
-                }
+                if (inb) zc_store(a, o, ls, cs, th, ab, vd, mk);
             }
             }
             ZC_T(3)
@@ -466,20 +302,14 @@ void zc_cfar_kernel(ZcArgs a) {
         if (wv == 0) { ZC_T(2) } else { ZC_T(4) }
     }
     // ---- gates still open at the end: gate_end = n, gate_mask[gate_start:n] ----
-    if (wv >= 1 && !idle_w) {
+    if (wv >= 1) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            const int s = hi + ZHE * j;
+            const int s = hi + ZH * j;
             if (s >= ns) break;
-            ZGate& G = g[j];
+            ZcGate& G = g[j];
             if (G.open) {
-                if (a.ev && G.nev < a.max_ev && lane < 4) {
-                    int64_t* r = a.ev + ((b0 + s) * (int64_t)a.max_ev + G.nev) * 4;
-                    const int64_t ds = G.pk - a.reflen + 1 > 0 ? G.pk - a.reflen + 1 : 0;
-                    r[lane] = lane == 0 ? G.pk : lane == 1 ? G.gs : lane == 2 ? n : ds;
-                    if (lane == 0 && a.ev_v) a.ev_v[(b0 + s) * (int64_t)a.max_ev + G.nev] = G.pv;
-                }
-                G.nev += 1;
+                ZC_EVENT(a, G, b0 + s, n, lane);
                 if (lane == 0 && a.gate_mask) a.gate_mask[(b0 + s) * n + G.gs] = 1;
             }
             if (lane == 0 && a.n_ev) a.n_ev[b0 + s] = G.nev;
@@ -516,7 +346,7 @@ int ofs_zc_cfar_try(const double* corr_mag, int64_t B, int64_t n, int W, double 
     if (plan == 0) return 0;
     ZcArgs a{corr_mag, B, n, W, tv, scale, minmag, reflen, Hp, local_sum, corr_scaled, thresh_scaled,
              above, valid, gate_mask, max_ev, n_ev, ev, ev_v};
-    constexpr int SD = OFS_ZC_S, HD = OFS_ZC_H, SR = OFS_ZC_S_REG, HR = OFS_ZC_H_REG;
+    constexpr int SD = ZS_DMA, HD = ZH_DMA, SR = ZS_REG, HR = ZH_REG;
     const dim3 gd((unsigned)((B + SD - 1) / SD)), gr((unsigned)((B + SR - 1) / SR));
     if (plan == 3) hipLaunchKernelGGL((zc_cfar_kernel<true, SD, HD, true>), gd, dim3(64 * (1 + HD)), 0, st, a);
     else if (plan == 2) hipLaunchKernelGGL((zc_cfar_kernel<true, SD, HD, false>), gd, dim3(64 * (1 + HD)), 0, st, a);

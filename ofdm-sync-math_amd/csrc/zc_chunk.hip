@@ -3,9 +3,13 @@
 // gate events that closed among them; what the next call needs stays in a caller-owned state buffer.
 //
 // The kernel is the register-staged form of zc_cfar_kernel (zc_cfar.hip) - walker wave, helper waves
-// one chunk behind, one LDS-only barrier per 128-sample chunk - COPIED here so that the one-shot
-// kernels' instruction streams cannot change: zc_walk (zc_walk_chunk there), the load / stage pipeline,
-// the helpers' flag pass and stores.  Keep the copies in step by hand.  What differs:
+// one chunk behind, one LDS-only barrier per 128-sample chunk.  What the two kernels have in common
+// is in zc_tiles.h and used by both: the geometry, the walker's recursion, the gate record, the CFAR
+// decision, the event record, the row stores and the barrier (each checked to leave all four kernels'
+// instruction text as it was).  Two parts have a sibling in zc_cfar_kernel that
+// is written out there too, because they differ: the load / stage pair (here c[i - W] comes from the
+// ring) and the loops of the flag pass (tile slots rotated, not divided; valid from vfrom[j], not W).
+// A change to either is looked at on both sides.  What differs:
 //
 // HISTORY.  The state keeps the last W magnitudes as a ring indexed by the absolute sample: c[n] lives
 // in slot n mod W, which is the slot that held c[n - W].  The walker's c[i - W] tile reads the ring
@@ -29,18 +33,14 @@
 //   that owns the stream.
 #include "ofs_common.h"
 #include "ofdmsync.h"
+#include "zc_tiles.h"
 
 using namespace ofs;
 
 namespace {
 
-constexpr int YS = 8;             // streams per workgroup (walker lanes); zc_cfar.hip OFS_ZC_S_REG
-constexpr int YH = 3;             // helper waves; zc_cfar.hip OFS_ZC_H_REG
-constexpr int YR = 2;             // 64-sample rows per chunk
-constexpr int YC = 64 * YR;       // samples per chunk
-constexpr int YP = YC + 2;        // LDS row pitch in doubles
-constexpr int YB = 8;             // walker: samples per LDS batch
-constexpr int NJ = (YS + YH - 1) / YH;   // streams per helper wave
+constexpr int ZS = ZS_REG, ZH = ZH_REG;   // streams per workgroup (walker lanes), helper waves
+constexpr int NJ = (ZS + ZH - 1) / ZH;   // streams per helper wave
 
 struct ZcChunkHdr {
     double acc;                   // running sum after the last sample
@@ -64,49 +64,6 @@ struct ZcChunkArgs {
     int fin;
 };
 
-struct YGate {
-    int64_t last_above, gs, pk;
-    double pv;
-    int open, nev;
-};
-
-template <class T>
-__device__ __forceinline__ void yc_st(T* p, T v) { __builtin_nontemporal_store(v, p); }
-
-// walker: the exact left-to-right recursion of RunningSum.step over one full chunk of this lane's
-// stream (zc_walk_chunk of zc_cfar.hip without its window-not-full form: see HISTORY above)
-__device__ __forceinline__ void zc_walk(const double* x, const double* o, double* r, double& acc) {
-#pragma clang fp contract(off)
-    double2 xv[YB / 2], ov[YB / 2];
-#pragma unroll
-    for (int j = 0; j < YB / 2; ++j) {
-        xv[j] = reinterpret_cast<const double2*>(x)[j];
-        ov[j] = reinterpret_cast<const double2*>(o)[j];
-    }
-#pragma unroll
-    for (int bb = 0; bb < YC / YB; ++bb) {
-        double2 xn[YB / 2], on[YB / 2];
-        if (bb + 1 < YC / YB) {
-#pragma unroll
-            for (int j = 0; j < YB / 2; ++j) {
-                xn[j] = reinterpret_cast<const double2*>(x + (bb + 1) * YB)[j];
-                on[j] = reinterpret_cast<const double2*>(o + (bb + 1) * YB)[j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < YB / 2; ++j) {
-            double2 rr;
-            acc = (acc + xv[j].x) - ov[j].x; rr.x = acc;
-            acc = (acc + xv[j].y) - ov[j].y; rr.y = acc;
-            reinterpret_cast<double2*>(r + bb * YB)[j] = rr;
-        }
-        if (bb + 1 < YC / YB) {
-#pragma unroll
-            for (int j = 0; j < YB / 2; ++j) { xv[j] = xn[j]; ov[j] = on[j]; }
-        }
-    }
-}
-
 // diagnostic builds (-DOFS_ZC_CHUNK_TIMING=1, tools/zc_chunk_phase.py): s_memtime ticks per role and
 // phase, summed over the waves of the role: [0..6] walker wave, [8..14] helper waves;
 // phase 0 entry (header reads, first tiles), 1 tile loads + staging, 2 chain / helper work, 3 chunk barrier,
@@ -123,23 +80,23 @@ __device__ unsigned long long zcc_prof[16];
 #define YC_T(i)
 #endif
 
-__global__ __launch_bounds__(64 * (1 + YH))
+__global__ __launch_bounds__(64 * (1 + ZH))
 void zc_chunk_kernel(ZcChunkArgs a) {
 #pragma clang fp contract(off)
 #if OFS_ZC_CHUNK_TIMING
     long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tprev = __builtin_amdgcn_s_memtime();
 #endif
-    __shared__ double tc[3][YS][YP];      // c
-    __shared__ double to[2][YS][YP];      // c[n - W]: ring, then the chunk itself
-    __shared__ double ta[2][YS][YP];      // running sum after sample i
+    __shared__ double tc[3][ZS][ZP];      // c
+    __shared__ double to[2][ZS][ZP];      // c[n - W]: ring, then the chunk itself
+    __shared__ double ta[2][ZS][ZP];      // running sum after sample i
     const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // 0 = walker, 1..YH = helpers
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // 0 = walker, 1..ZH = helpers
     const int hi = wv - 1;
-    const int64_t b0 = (int64_t)blockIdx.x * YS;
-    const int ns = (int)min((int64_t)YS, a.B - b0);          // streams of this workgroup
+    const int64_t b0 = (int64_t)blockIdx.x * ZS;
+    const int ns = (int)min((int64_t)ZS, a.B - b0);          // streams of this workgroup
     const int64_t Tc = a.Tc;
-    const int64_t nch = (Tc + YC - 1) / YC;
+    const int64_t nch = (Tc + ZC - 1) / ZC;
     const int W = a.W;
     auto hdr_of = [&](int s) { return reinterpret_cast<ZcChunkHdr*>(a.state + (b0 + s) * a.state_bytes); };
     auto ring_of = [&](int s) { return reinterpret_cast<double*>(a.state + (b0 + s) * a.state_bytes + sizeof(ZcChunkHdr)); };
@@ -149,19 +106,20 @@ void zc_chunk_kernel(ZcChunkArgs a) {
     auto slot_of = [&](int s) {
         return __builtin_amdgcn_readfirstlane((int)((uint64_t)hdr_of(s)->n_seen % (uint64_t)W));
     };
-    int r0[YS];                                               // ring slot of the call's first sample
+    int r0[ZS];                                               // ring slot of the call's first sample
     const double* cw = a.mag + b0 * a.ld;
     if (wv == 0) {
 #pragma unroll
-        for (int s = 0; s < YS; ++s) r0[s] = s < ns ? slot_of(s) : 0;
+        for (int s = 0; s < ZS; ++s) r0[s] = s < ns ? slot_of(s) : 0;
     }
-    double pc[YR][YS], po[YR][YS];
+    // load / stage: zc_cfar_kernel's register pair with the ring as the source of c[i - W] for i < W
+    double pc[ZR][ZS], po[ZR][ZS];
     auto load = [&](int64_t q) {
 #pragma unroll
-        for (int rr = 0; rr < YR; ++rr) {
-            const int64_t i = q * YC + 64 * rr + lane;
+        for (int rr = 0; rr < ZR; ++rr) {
+            const int64_t i = q * ZC + 64 * rr + lane;
 #pragma unroll
-            for (int s = 0; s < YS; ++s) {
+            for (int s = 0; s < ZS; ++s) {
                 const bool ok = s < ns && i < Tc;
                 pc[rr][s] = ok ? cw[s * a.ld + i] : 0.0;
                 double o = 0.0;
@@ -180,22 +138,22 @@ void zc_chunk_kernel(ZcChunkArgs a) {
     };
     auto stage = [&](int q3, int q2) {                        // tile slots of the chunk: q mod 3, q mod 2
 #pragma unroll
-        for (int rr = 0; rr < YR; ++rr)
+        for (int rr = 0; rr < ZR; ++rr)
 #pragma unroll
-            for (int s = 0; s < YS; ++s) {
+            for (int s = 0; s < ZS; ++s) {
                 tc[q3][s][64 * rr + lane] = pc[rr][s];
                 to[q2][s][64 * rr + lane] = po[rr][s];
             }
     };
 
-    // helpers: the gate machines and sample counts of their streams hi, hi + YH, ...
-    YGate g[NJ];
+    // helpers: the gate machines and sample counts of their streams hi, hi + ZH, ...
+    ZcGate g[NJ];
     int64_t n0[NJ], vfrom[NJ];                                // first sample's absolute index; first valid i
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         g[j].last_above = 0; g[j].gs = 0; g[j].pk = 0; g[j].pv = 0.0; g[j].open = 0; g[j].nev = 0;
         n0[j] = 0; vfrom[j] = 0;
-        const int s = hi + YH * j;
+        const int s = hi + ZH * j;
         if (wv >= 1 && s < ns) {
             const ZcChunkHdr h = *hdr_of(s);
             g[j].last_above = h.last_above; g[j].gs = h.gs; g[j].pk = h.pk; g[j].pv = h.pv; g[j].open = h.open != 0;
@@ -206,18 +164,12 @@ void zc_chunk_kernel(ZcChunkArgs a) {
     double acc = 0.0;                                         // walker lane s < ns: stream b0 + s
     if (wv == 0 && lane < ns) acc = hdr_of(lane)->acc;
 
-    // LDS-only barrier: the helpers' global stores are never waited for (zc_cfar.hip)
-    auto lds_barrier = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    };
     if (wv == 0) {
         load(0);
         stage(0, 0);
         if (1 < nch) load(1);
     }
-    lds_barrier();
+    zc_lds_barrier();
     YC_T(0)
     int c3 = 0;                                               // q mod 3, rotated (no 64-bit division per chunk)
     for (int64_t q = 0; q <= nch; ++q) {
@@ -228,13 +180,13 @@ void zc_chunk_kernel(ZcChunkArgs a) {
             if (q + 2 < nch) load(q + 2);
             YC_T(1)
             // ---- walker: the exact left-to-right recursion of RunningSum.step ----
-            if (q < nch && lane < YS) {
-                const int cnt = (int)min((int64_t)YC, Tc - q * YC);
+            if (q < nch && lane < ZS) {
+                const int cnt = (int)min((int64_t)ZC, Tc - q * ZC);
                 const double* x = tc[c3][lane];
                 const double* o = to[c2][lane];
                 double* r = ta[c2][lane];
-                if (cnt == YC) {
-                    zc_walk(x, o, r, acc);
+                if (cnt == ZC) {
+                    zc_walk_chunk<ZC, false>(x, o, r, acc);
                 } else {
                     for (int u = 0; u < cnt; ++u) { acc = (acc + x[u]) - o[u]; r[u] = acc; }
                 }
@@ -245,28 +197,29 @@ void zc_chunk_kernel(ZcChunkArgs a) {
             const int64_t qc = q - 1;
             const int q3 = p3, q2 = c2 ^ 1;
             // pass 1: the flags of every (row, stream) of this wave.  A chunk with no above sample and
-            // no open gate needs no gate logic: its gate_mask rows are 0
+            // no open gate needs no gate logic: its gate_mask rows are 0.  (The loops are zc_cfar_kernel's
+            // with the tile slots rotated and valid = i >= vfrom[j]; as one function they changed all four
+            // kernels by 1 - 5 instructions, see there.)
             bool quiet = true;
-            double cv[YR][NJ], lv[YR][NJ];
-            uint64_t am[YR][NJ];
+            double cv[ZR][NJ], lv[ZR][NJ];
+            uint64_t am[ZR][NJ];
 #pragma unroll
-            for (int rr = 0; rr < YR; ++rr)
+            for (int rr = 0; rr < ZR; ++rr)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    const int s = hi + YH * j;
+                    const int s = hi + ZH * j;
                     const int sr = s < ns ? s : 0;
                     cv[rr][j] = tc[q3][sr][64 * rr + lane];
                     lv[rr][j] = ta[q2][sr][64 * rr + lane];
                 }
 #pragma unroll
-            for (int rr = 0; rr < YR; ++rr) {
-                const int64_t i = qc * YC + 64 * rr + lane;
+            for (int rr = 0; rr < ZR; ++rr) {
+                const int64_t i = qc * ZC + 64 * rr + lane;
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    const int s = hi + YH * j;
+                    const int s = hi + ZH * j;
                     const bool vd = (i < Tc) & (i >= vfrom[j]);
-                    const bool ab = (s < ns) & vd & (cv[rr][j] * a.scale >= lv[rr][j] * a.tv) & (cv[rr][j] >= a.minmag);
-                    am[rr][j] = __ballot(ab);
+                    am[rr][j] = zc_above(a, (s < ns) & vd, cv[rr][j], lv[rr][j]);
                     if (am[rr][j]) quiet = false;
                 }
             }
@@ -274,14 +227,14 @@ void zc_chunk_kernel(ZcChunkArgs a) {
             for (int j = 0; j < NJ; ++j)
                 if (g[j].open) quiet = false;
 #pragma unroll
-            for (int rr = 0; rr < YR; ++rr) {
-                const int64_t i0 = qc * YC + 64 * rr;             // call-local index of the row's lane 0
+            for (int rr = 0; rr < ZR; ++rr) {
+                const int64_t i0 = qc * ZC + 64 * rr;             // call-local index of the row's lane 0
                 const int64_t i = i0 + lane;
                 const bool inb = i < Tc;
                 const int cnt = (int)min((int64_t)64, Tc - i0);   // samples of the row (<= 0: none)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    const int s = hi + YH * j;
+                    const int s = hi + ZH * j;
                     if (s >= ns) break;
                     const double c = cv[rr][j];
                     const double ls = lv[rr][j];
@@ -291,7 +244,7 @@ void zc_chunk_kernel(ZcChunkArgs a) {
                     const int64_t o = (b0 + s) * Tc + i;
                     uint64_t mk = 0;                              // gate_mask bits of the row
                     if (!quiet && cnt > 0) {
-                        YGate& G = g[j];
+                        ZcGate& G = g[j];
                         const int64_t base = n0[j] + i0;          // absolute index of the row's lane 0
                         int pos = 0;
                         while (pos < cnt) {
@@ -312,6 +265,9 @@ void zc_chunk_kernel(ZcChunkArgs a) {
                                 }
                                 const int e = cl >= 0 ? cl : cnt - 1;            // the gate's samples here: [pos, e]
                                 mk |= (e >= 63 ? ~0ull : ((1ull << (e + 1)) - 1)) & ~((1ull << pos) - 1);
+                                // zc_peak of zc_tiles.h written out: calling it here folds one scalar sign
+                                // extension (8572 -> 8571 instructions) and a Tc = 1024 push then measured
+                                // 0.0772 ms against the parent's 0.0765 - 0.0767 (profiles/zc_chunked_ab.jsonl)
                                 const bool in = lane >= pos && lane <= e;
                                 const double m = wave_max(in ? c : -__builtin_huge_val());
                                 if (m > G.pv) {
@@ -319,13 +275,8 @@ void zc_chunk_kernel(ZcChunkArgs a) {
                                     G.pv = m; G.pk = base + __builtin_ctzll(at);
                                 }
                                 if (cl >= 0) {
-                                    if (a.ev && G.nev < a.max_ev && lane < 4) {
-                                        int64_t* r = a.ev + ((b0 + s) * (int64_t)a.max_ev + G.nev) * 4;
-                                        const int64_t ds = G.pk - a.reflen + 1 > 0 ? G.pk - a.reflen + 1 : 0;
-                                        r[lane] = lane == 0 ? G.pk : lane == 1 ? G.gs : lane == 2 ? base + cl : ds;
-                                        if (lane == 0 && a.ev_v) a.ev_v[(b0 + s) * (int64_t)a.max_ev + G.nev] = G.pv;
-                                    }
-                                    G.nev += 1; G.open = 0; G.pv = 0.0;
+                                    ZC_EVENT(a, G, b0 + s, base + cl, lane);
+                                    G.open = 0; G.pv = 0.0;
                                     pos = cl + 1;
                                 } else {
                                     pos = cnt;
@@ -340,19 +291,12 @@ void zc_chunk_kernel(ZcChunkArgs a) {
                             }
                         }
                     }
-                    if (inb) {
-                        if (a.local_sum) yc_st(&a.local_sum[o], ls);
-                        if (a.corr_scaled) yc_st(&a.corr_scaled[o], cs);
-                        if (a.thresh_scaled) yc_st(&a.thresh_scaled[o], th);
-                        if (a.above) yc_st(&a.above[o], (uint8_t)((abm >> lane) & 1));
-                        if (a.valid) yc_st(&a.valid[o], (uint8_t)vd);
-                        if (a.gate_mask) yc_st(&a.gate_mask[o], (uint8_t)((mk >> lane) & 1));
-                    }
+                    if (inb) zc_store(a, o, ls, cs, th, (abm >> lane) & 1, vd, (mk >> lane) & 1);
                 }
             }
             YC_T(2)
         }
-        lds_barrier();
+        zc_lds_barrier();
         YC_T(3)
         c3 = n3;
     }
@@ -365,14 +309,14 @@ void zc_chunk_kernel(ZcChunkArgs a) {
     for (int s = 0; s < ns; ++s) {
         double* ring = ring_of(s);
         if (a.fin) {
-            for (int k = (int)threadIdx.x; k < W; k += 64 * (1 + YH)) ring[k] = 0.0;
+            for (int k = (int)threadIdx.x; k < W; k += 64 * (1 + ZH)) ring[k] = 0.0;
         } else {
             const int rp = slot_of(s);
             const int m = (int)min((int64_t)W, Tc);
             int start = Tc > W ? rp + a.tcm : rp;                 // slot of sample Tc - m
             start = start >= W ? start - W : start;
             const double* src = cw + s * a.ld + (Tc - m);
-            for (int k = (int)threadIdx.x; k < m; k += 64 * (1 + YH)) {
+            for (int k = (int)threadIdx.x; k < m; k += 64 * (1 + ZH)) {
                 int slot = start + k;
                 slot = slot >= W ? slot - W : slot;
                 ring[slot] = src[k];
@@ -388,22 +332,16 @@ void zc_chunk_kernel(ZcChunkArgs a) {
     } else {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            const int s = hi + YH * j;
+            const int s = hi + ZH * j;
             if (s >= ns) break;
-            YGate& G = g[j];
+            ZcGate& G = g[j];
             const int64_t b = b0 + s;
             if (lane == 0) a.open_start[b] = G.open ? G.gs : -1;
             if (a.fin && G.open) {                             // closes at the stream's sample count
-                if (a.ev && G.nev < a.max_ev && lane < 4) {
-                    int64_t* r = a.ev + (b * (int64_t)a.max_ev + G.nev) * 4;
-                    const int64_t ds = G.pk - a.reflen + 1 > 0 ? G.pk - a.reflen + 1 : 0;
-                    r[lane] = lane == 0 ? G.pk : lane == 1 ? G.gs : lane == 2 ? n0[j] + Tc : ds;
-                    if (lane == 0 && a.ev_v) a.ev_v[b * (int64_t)a.max_ev + G.nev] = G.pv;
-                }
-                G.nev += 1;
+                ZC_EVENT(a, G, b, n0[j] + Tc, lane);
                 // gate_mask[gate_start:n] of the reference: the start sample, where it lies in this call
                 if (lane == 0 && a.gate_mask && G.gs >= n0[j] && G.gs - n0[j] < Tc)
-                    yc_st(&a.gate_mask[b * Tc + (G.gs - n0[j])], (uint8_t)1);
+                    zc_st(&a.gate_mask[b * Tc + (G.gs - n0[j])], (uint8_t)1);
             }
             if (lane == 0) {
                 a.n_ev[b] = G.nev;
@@ -457,7 +395,7 @@ int32_t ofs_zc_detect_chunk(const double* corr_mag, int64_t ld_mag, int64_t B, i
         (max_events > 0 && B > 0 && (!ev_int || !ev_peak)))
         return OFS_EINVAL;
     if (B == 0) return OFS_OK;
-    const int64_t nblk = (B + YS - 1) / YS;
+    const int64_t nblk = (B + ZS - 1) / ZS;
     if (nblk > 0x7fffffffll) return OFS_EINVAL;
     ZcChunkArgs a{};
     a.mag = corr_mag; a.ld = ld_mag; a.B = B; a.Tc = Tc;
@@ -471,7 +409,7 @@ int32_t ofs_zc_detect_chunk(const double* corr_mag, int64_t ld_mag, int64_t B, i
     a.max_ev = max_events; a.n_ev = n_events; a.ev = max_events > 0 ? ev_int : nullptr;
     a.ev_v = max_events > 0 ? ev_peak : nullptr;
     a.open_start = open_gate_start; a.fin = final != 0;
-    hipLaunchKernelGGL(zc_chunk_kernel, dim3((unsigned)nblk), dim3(64 * (1 + YH)), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(zc_chunk_kernel, dim3((unsigned)nblk), dim3(64 * (1 + ZH)), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
 }
 

@@ -2,6 +2,7 @@
 sync_aa detector (ofs_aa_detect) on one shape, lib order rotated every round.  Diagnostic only.
 
     python tools/lib_ab.py --libs build/libofdmsync_a.so,build/libofdmsync_b.so --B 65536 --T 4096 --L 512 --na 1
+    python tools/lib_ab.py --op zc --libs PARENT/libofdmsync.so,NEW/libofdmsync.so --B 4096 --T 16384 --L 512
 """
 from __future__ import annotations
 
@@ -34,10 +35,13 @@ def main():
     ap.add_argument("--head-resident", action="store_true",
                     help="aa: P/M heads zeroed once, calls through ofs_aa_detect_ex with OFS_AA_HEAD_RESIDENT")
     ap.add_argument("--no-check", action="store_true", help="variants may differ in rounding (no bit-equality check)")
-    ap.add_argument("--op", choices=("aa", "scminn", "sc", "comb", "minn", "zcfreq"), default="aa",
+    ap.add_argument("--op", choices=("aa", "scminn", "sc", "comb", "minn", "zcfreq", "zc"), default="aa",
                     help="aa: ofs_aa_detect; scminn: ofs_sc_minn_metric (cfg4 fused S&C + Minn, N = 2 L); zcfreq: "
-                         "ofs_zc_freq_metric on c64 -> f32 (--na branches, N = 4 L, cp = L, the ZC template)")
+                         "ofs_zc_freq_metric on c64 -> f32 (--na branches, N = 4 L, cp = L, the ZC template); zc: "
+                         "ofs_zc_detect on every fused plan and ofs_zc_detect_chunk (W = 4 L, hysteresis L / 2)")
     a = ap.parse_args()
+    if a.op == "zc":
+        return zc(a)
     if a.op == "zcfreq":
         return zcfreq(a)
     if a.op != "aa":
@@ -193,6 +197,87 @@ def zcfreq(a):
         ms = statistics.median(times[name])
         print(json.dumps(dict(lib=name, op=a.op, shape=[B, nb, T, N, cp], ms_median=round(ms, 4),
                               ms_all=[round(t, 4) for t in times[name]])), flush=True)
+
+
+def zc(a):
+    """zc_v2 CFAR + gate on B x T float64 magnitudes (--B 4096 --T 16384 --L 512: the shape of
+    tools/zc_chunk_ab.py): the one-shot call on its three fused plans and the resumable call in three
+    pushes, every output poisoned before each library's run and compared bit for bit between them."""
+    from zc_chunk_ab import FRAC, MAX_EV, MIN_MAG, REFLEN, make_mag
+    dev = torch.device("cuda", 0)
+    B, n, W, hyst = a.B, a.T, 4 * a.L, a.L // 2
+    tv = int(4.0 * (1 << FRAC) / W)
+    mag = make_mag(B, n, dev)
+    st = torch.cuda.current_stream(dev)
+    libs = []
+    for p in a.libs.split(","):
+        l = ctypes.CDLL(os.path.abspath(p))
+        _lib._declare(l)
+        libs.append((p, l))                                      # the path as given: in-tree libraries share a file name
+    f64, u8 = torch.float64, torch.uint8
+    cuts = [0, n // 2, n // 2 + n // 4 + 37, n]                   # pushes: a whole number of chunks, an odd one, the rest
+    sb = libs[0][1].ofs_zc_chunk_state_bytes(W)
+    cases = [("events + mask", {}, False, False), ("state arrays", {}, True, False),
+             ("register tiles, state arrays", {"ZC_NODMA": 1}, True, False), ("chunked, state arrays", {}, True, True)]
+    for name, var, state, chunked in cases:
+        arr = [torch.empty((B, n), dtype=dt, device=dev) if state else None for dt in (f64, f64, f64, u8, u8)]
+        gm = torch.empty((B, n), dtype=u8, device=dev)
+        n_ev = torch.empty((B,), dtype=torch.int32, device=dev)
+        ev = torch.empty((B, MAX_EV, 4), dtype=torch.int64, device=dev)
+        pv = torch.empty((B, MAX_EV), dtype=f64, device=dev)
+        og = torch.empty((B,), dtype=torch.int64, device=dev)
+        stt = torch.zeros((B, sb), dtype=u8, device=dev)
+        outs = [t for t in arr if t is not None] + [gm, n_ev, ev, pv, og]
+        # a push writes [B][Tc] blocks: one set of buffers per push, copied into the [B][n] arrays afterwards
+        blk = [[None if t is None else torch.empty((B, e - b), dtype=t.dtype, device=dev) for t in arr + [gm]]
+               for b, e in zip(cuts, cuts[1:])] if chunked else []
+
+        def run(l):
+            if not chunked:
+                return l.ofs_zc_detect(mag.data_ptr(), B, n, W, tv, FRAC, MIN_MAG, REFLEN, hyst, *[_lib.ptr(t) for t in arr],
+                                       gm.data_ptr(), MAX_EV, n_ev.data_ptr(), ev.data_ptr(), pv.data_ptr(), st.cuda_stream)
+            rc = 0
+            for k, (b, e) in enumerate(zip(cuts, cuts[1:])):
+                rc |= l.ofs_zc_detect_chunk(mag.data_ptr() + 8 * b, n, B, e - b, W, tv, FRAC, MIN_MAG, REFLEN, hyst,
+                                            stt.data_ptr(), *[_lib.ptr(t) for t in blk[k]], MAX_EV, n_ev.data_ptr(),
+                                            ev.data_ptr(), pv.data_ptr(), og.data_ptr(), int(e == n), st.cuda_stream)
+            return rc
+
+        times, ref = {nm: [] for nm, _ in libs}, None
+        for r in range(a.rounds):
+            for nm, l in libs[r % len(libs):] + libs[:r % len(libs)]:
+                for k, v in var.items():
+                    l.ofs_debug_set_variant(k.encode(), v)
+                plan = l.ofs_zc_detect_plan(n, W, hyst, int(state), int(mag.data_ptr() % 16 == 0))
+                for t in outs + [t for row in blk for t in row if t is not None]:
+                    t.view(u8).fill_(0xA5)                       # every compared byte must be written by this library
+                ev.zero_()                                       # records past n_events are never written
+                pv.zero_()
+                assert run(l) == 0
+                torch.cuda.synchronize()
+                for k, (b, e) in enumerate(zip(cuts, cuts[1:]) if chunked else ()):
+                    for t, part in zip(arr + [gm], blk[k]):
+                        if t is not None:
+                            t[:, b:e] = part
+                got = [t.clone() for t in (outs if chunked else outs[:-1])]   # open_gate_start: the resumable call's
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(a.steps):
+                    run(l)
+                e1.record(st)
+                torch.cuda.synchronize()
+                times[nm].append(e0.elapsed_time(e1) / a.steps)
+                l.ofs_debug_reset_variants()
+                if ref is None:
+                    ref = got
+                elif not a.no_check:
+                    for i, (x, y) in enumerate(zip(ref, got)):
+                        assert torch.equal(x.view(u8), y.view(u8)), f"{nm}: {name}: output {i} differs"
+        for nm, _ in libs:
+            ms = statistics.median(times[nm])
+            print(json.dumps(dict(lib=nm, op="zc", case=name, plan=plan, shape=[B, n, W, hyst], ms_median=round(ms, 4),
+                                  ms_all=[round(t, 4) for t in times[nm]], bit_equal=not a.no_check,
+                                  events_mean=round(float(n_ev.float().mean()), 3))), flush=True)
 
 
 if __name__ == "__main__":
