@@ -223,6 +223,54 @@ int32_t ofs_aa_detect_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_
                             int32_t final, void* stream);
 
 /*
+ * Resumable chunked [A][A] detection for complex64 streams: the chunk-fed form of the fp32 fast path
+ * (ofs_aa_detect(OFS_C64, ..., OFS_FP32), ofs_aa_plan 1000-1199).  Same contract as ofs_aa_detect_chunk:
+ * caller-owned state [B][ofs_aa_chunk_f32_state_bytes(n_ant, L)], 16-byte aligned, ALL-ZERO BYTES ARE A
+ * FRESH STREAM; events from slot 0 of every call with absolute int64 indices (frame_start =
+ * peak_index - 2L + 1); n_events exact even above max_events; an open gate is carried until final != 0,
+ * which closes it at the stream's sample count and leaves a fresh state; Tc = 0 with final is a flush;
+ * calls are stream-ordered, never synchronise with the host, allocate nothing and keep no global state.
+ *   x       [B][n_ant][Tc] complex64 (this call's chunk); n_ant 1-2; L 128, 256, 512 or 1024.
+ *   P, R, M, valid  [B][Tc] c64 / f32 / f32 / uint8, each nullable.
+ *   Tc      1 .. ofs_aa_chunk_f32_max_samples(n_ant, L) = 2^30 (in-call positions - 2L + 127 history
+ *           samples, the chunk and a gate offset of at most OFS_AA_CHUNK_MAX_HYSTERESIS + 128 - stay
+ *           below 2^31).
+ *   n_ant, L, threshold, hysteresis and detect must not change between the calls of a stream.
+ * EQUIVALENCE GUARANTEE.  For any split of a stream of T samples into chunks, the concatenated P, R, M,
+ * valid and the sequence of events (the last call final) - integers and reals - equal BIT FOR BIT what
+ * one ofs_aa_detect(OFS_C64, ..., OFS_FP32) call WITH P, R AND M PRESENT returns on the whole stream on
+ * plans 1000-1199.  The arithmetic is that of this storing call (rows of 128 samples, 2 per lane, fp64
+ * row scans), whether or not P/R/M are passed here.  The one-shot DETECT-ONLY call (no P/R/M/valid)
+ * uses another row width and fp32 scans and is NOT the yardstick: its events may differ from these
+ * where the decision is a near-tie, exactly as they may from the one-shot storing call's.
+ * For n < L the outputs are P = M = +0.0 and valid = 0 for any input, NaN and Inf included: those rows
+ * take the no-lag form by their absolute index, nothing is multiplied with a zero history.  Behind
+ * non-finite samples an output word is a NaN exactly where the one-shot call's is, with the same
+ * payload; its SIGN bit is outside the guarantee, because the one-shot kernels of plans 10xx and 11xx
+ * do not agree on it among themselves (two NaNs of opposite sign in one add).
+ * STREAM LENGTH.  The state carries the fp64 running sums C of the row totals since sample 0 (of the
+ * lagged products and of the energy), and a window's "rows between" term is a difference of two of
+ * them, so its absolute error grows as 2^-53 * |C|.  At unit amplitude |C| is about the sample count n,
+ * and a window sum is about L with an fp32 ulp of 2^-23 * L: the carried error reaches one such ulp at
+ * n = 2^30 * L samples (2^37 for L = 128, 2^40 for L = 1024: hours at 100 MS/s).  Up to there the
+ * guarantee above is what bounds the error (it is the one-shot call's); beyond it the outputs still
+ * equal what a one-shot call of that length would compute, but that value itself degrades.  final (or
+ * zeroing the state) restarts C.  Energy far above unit amplitude shortens the span in proportion.
+ * OFS_EINVAL (before any launch): n_ant outside 1-2, an L outside the table, Tc < 0 or above the limit,
+ * Tc = 0 without final, B < 0, a null or misaligned state with B > 0, a null x with B * Tc > 0,
+ * hysteresis > OFS_AA_CHUNK_MAX_HYSTERESIS, detect with a null n_events or with null event arrays while
+ * max_events > 0.  There is no fall-back to the general engine.  The two helpers return OFS_EINVAL (< 0)
+ * for an unsupported n_ant or L; the state size is a multiple of 16.
+ */
+int64_t ofs_aa_chunk_f32_state_bytes(int32_t n_ant, int32_t L);
+int64_t ofs_aa_chunk_f32_max_samples(int32_t n_ant, int32_t L);
+int32_t ofs_aa_detect_chunk_f32(const void* x, int64_t B, int32_t n_ant, int64_t Tc, int32_t L,
+                                void* state, void* P, void* R, void* M, uint8_t* valid,
+                                int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
+                                int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
+                                int32_t final, void* stream);
+
+/*
  * Schmidl-Cox half-symbol metric, reference index convention d = 0 .. T-N.
  * r_mode 0 replaces sc.sc_streaming_metric (sc.py:42-78; R = second-half energy);
  * r_mode 1 replaces combined_sc_min.schmidl_cox_streaming_metric (combined_sc_min.py:116-164;

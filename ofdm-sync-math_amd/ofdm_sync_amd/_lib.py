@@ -72,6 +72,11 @@ def _declare(lib):
         "ofs_aa_detect_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, P, P, P, P, P,
                                           c_int32, c_double, c_int32, c_double, c_int32, P, P, P,
                                           c_int32, P]),
+        "ofs_aa_chunk_f32_state_bytes": (c_int64, [c_int32, c_int32]),
+        "ofs_aa_chunk_f32_max_samples": (c_int64, [c_int32, c_int32]),
+        "ofs_aa_detect_chunk_f32": (c_int32, [P, c_int64, c_int32, c_int64, c_int32, P, P, P, P, P,
+                                              c_int32, c_double, c_int32, c_double, c_int32, P, P, P,
+                                              c_int32, P]),
         "ofs_sc_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,
                                     c_int32, P, P, P, P]),
         "ofs_minn_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,
