@@ -749,18 +749,31 @@ int32_t ofs_zc_detect_chunk(const double* corr_mag, int64_t ld_mag, int64_t B, i
  * Metrics are [B][n] device arrays; `precision` names their element type (OFS_FP32 = float,
  * OFS_FP64 = double).  Smoothed outputs are f64.  Per-stream `status` reports what the
  * reference would do: >= 0 ok (for ofs_plateau_end the branch taken), < 0 it raises ValueError.
+ *
+ * Non-finite samples are decided as numpy decides them.  Every argmax is np.argmax: NaN is the
+ * maximum, the first index wins among equals (NaNs included), and -inf is a value like any other,
+ * so an all-NaN or all -inf stream answers index 0 and no index is ever out of [0, n).  Where the
+ * reference takes np.max, a NaN maximum makes `max > 0`, `max <= 0` and every comparison with a
+ * level derived from it false, and the reference's branch for that is taken.  The sign bit and
+ * payload of a NaN output are not specified.
  */
 
 /* minn._trailing_average / combined_sc_min._trailing_average (minn.py:115-128,
  * combined_sc_min.py:167-180) of max(x, 0) when clip_negative != 0 (minn.py:149), else of x:
- * the reference's float64 running-sum recursion, sample by sample.  out: [B][n] f64. */
+ * the reference's float64 running-sum recursion, sample by sample.  out: [B][n] f64.
+ * np.maximum keeps NaN and turns -inf into 0; a NaN, or a +inf once it leaves the window
+ * (inf - inf), makes every later output NaN, as in the reference.  No status: never raises. */
 int32_t ofs_trailing_average(int32_t precision, const void* x, int64_t B, int64_t n, int32_t win,
                              int32_t clip_negative, double* out, void* stream);
 
 /* sc.find_plateau_end_from_metric (sc.py:81-146).  lookahead < 0 means None.  Ms: [B][max(n, w)]
  * f64 (numpy "same" convolution length); plateau_end: [B] int64; status: [B] int32 = branch
  * (1 drop below 95 %, 2 earliest long run above 60 %, 3 slope fallback, 4 fallback on an empty
- * window, 0 empty metric), -3 where numpy's broadcast would raise. */
+ * window, 0 empty metric), -3 where numpy's broadcast would raise (plateau_end is -1 then).
+ * A NaN in Ms (a NaN sample, or +inf and -inf in one window): the centre is the first NaN, the
+ * 95 % and 60 % tests fail, and the slope fallback's argmax takes the first NaN drop (branch 3 or
+ * 4, or -3).  +inf without NaN is its own 95 % level (branch 1 at the centre when cp_len > 1 and
+ * the centre is not last); all -inf likewise answers index 0, branch 1. */
 int32_t ofs_plateau_end(int32_t precision, const void* M, int64_t B, int64_t n, int32_t cp_len,
                         int32_t lookahead, int32_t smooth_win, double* Ms, int64_t* plateau_end,
                         int32_t* status, void* stream);
@@ -768,20 +781,30 @@ int32_t ofs_plateau_end(int32_t precision, const void* M, int64_t B, int64_t n, 
 /* minn.find_minn_peak (minn.py:131-205) on the trailing average Ms (ofs_trailing_average):
  * gate = longest run of Ms >= gate_threshold * max(Ms) (earliest on ties) cut to
  * [bound_lo, bound_hi) (0, n for no bounds); empty gate -> global argmax.  peak, gate_lo,
- * gate_hi: [B] int64 (gate_* nullable); status -1 empty metric, -2 no positive peak. */
+ * gate_hi: [B] int64 (gate_* nullable); status 0 ok, -1 empty metric (n == 0), -2 no positive
+ * peak (max(Ms) <= 0; peak is -1 and the gate 0, 0 for both).  A NaN in Ms is the maximum: it is
+ * neither <= 0 nor reached by any sample, so the gate is empty and peak = the first NaN, gate
+ * [peak, peak + 1), status 0.  +inf is an ordinary maximum (level = threshold * inf). */
 int32_t ofs_minn_peak(const double* Ms, int64_t B, int64_t n, double gate_threshold, int64_t bound_lo,
                       int64_t bound_hi, int64_t* peak, int64_t* gate_lo, int64_t* gate_hi, int32_t* status,
                       void* stream);
 
 /* The S&C gate of combined_sc_min.run_simulation (combined_sc_min.py:337-358):
  * mask = M_sc / max >= threshold (max > 0) else M_sc >= threshold, seeded with the argmax when
- * empty.  mask: [B][n] uint8 (nullable); span: [B][2] int64 = first, last + 1 (nullable). */
+ * empty.  mask: [B][n] uint8 (nullable); span: [B][2] int64 = first, last + 1 (nullable).
+ * No status: n == 0 writes span 0, 0.  A NaN sample makes the maximum NaN, so the comparison is the
+ * unnormalised one and NaN samples fail it; if nothing passes, the seed is the first NaN.  All
+ * -inf (or all NaN) gives the seed at index 0, span 0, 1.  With max = +inf, M_sc / max is 0 for
+ * finite samples and NaN (fails) for the +inf ones. */
 int32_t ofs_sc_gate(int32_t precision, const void* M_sc, int64_t B, int64_t n, double threshold,
                     uint8_t* mask, int64_t* span, void* stream);
 
 /* combined_sc_min._streaming_peak_detector (combined_sc_min.py:183-209) as used by
  * combined_sc_min.find_minn_peak (:212-259): first argmax (strict >) of Ms over the FIRST run of
- * mask within [bound_lo, bound_hi).  peak: [B] int64; status -1 empty gate region. */
+ * mask within [bound_lo, bound_hi).  peak: [B] int64; status 0 ok (n == 0: peak 0), -1 empty
+ * gate region (peak -1).  This is the reference's loop, not np.argmax: the run's first sample seeds
+ * the best value and only a strictly larger sample replaces it.  A run that starts with NaN
+ * answers its start; a NaN later in the run is skipped; a run of -inf answers its start. */
 int32_t ofs_segment_peak(const double* Ms, const uint8_t* mask, int64_t B, int64_t n, int64_t bound_lo,
                          int64_t bound_hi, int64_t* peak, int32_t* status, void* stream);
 

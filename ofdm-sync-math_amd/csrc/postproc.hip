@@ -14,6 +14,13 @@
 // mask) is a block reduction or an ordered chunk scan, so the integer answers equal the
 // reference's on the same metric values.  Arithmetic that feeds a comparison (0.95·max,
 // 0.6·peak, M/max, thr·max, the running sums) is the reference's own float64 expression.
+//
+// Non-finite metrics follow numpy: every argmax is np.argmax (NaN is the maximum, the first
+// index wins, -inf is a value like any other), so an index is never left at NONE when n > 0;
+// a maximum that is NaN (np.max) makes `> 0`, `<= 0` and every level comparison false and the
+// reference's branch for that is taken.  The segment peak is the reference's loop instead: the
+// run's first sample seeds the best value and only a strictly larger one replaces it, so a NaN
+// seed stays and a later NaN is skipped.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ofdmsync.h"
@@ -35,20 +42,31 @@ struct Red {
     int64_t b[PW];
 };
 
-// argmax with the smallest index on ties (np.argmax); v = -inf / i = NONE for empty lanes
+// np.argmax's order: does candidate (ov, oi) beat (v, i)?  NaN is the maximum, equal values
+// (two NaNs included) go to the smaller index, and i == NONE marks an empty slot that any
+// candidate beats, whatever its value (-inf too).
+__device__ __forceinline__ bool arg_beats(double ov, int64_t oi, double v, int64_t i) {
+    if (oi == NONE) return false;
+    if (i == NONE) return true;
+    const bool on = ov != ov, vn = v != v;
+    if (on || vn) return on && (!vn || oi < i);
+    return ov > v || (ov == v && oi < i);
+}
+
+// np.argmax over the block: v / i = NONE for empty lanes
 __device__ void block_argmax(double& v, int64_t& i, Red& r) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const double ov = __shfl_xor(v, off, 64);
         const int64_t oi = __shfl_xor(i, off, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+        if (arg_beats(ov, oi, v, i)) { v = ov; i = oi; }
     }
     if (lane == 0) { r.v[w] = v; r.i[w] = i; }
     __syncthreads();
     v = r.v[0]; i = r.i[0];
     for (int k = 1; k < PW / 64; ++k)
-        if (r.v[k] > v || (r.v[k] == v && r.i[k] < i)) { v = r.v[k]; i = r.i[k]; }
+        if (arg_beats(r.v[k], r.i[k], v, i)) { v = r.v[k]; i = r.i[k]; }
     __syncthreads();
 }
 
@@ -181,10 +199,10 @@ __global__ __launch_bounds__(PW) void plateau_kernel(PlArgs a) {
         double s = 0.0;
         for (int64_t j = j0; j <= j1; ++j) s += ld(M, j) * vw;
         Ms[i] = s;
-        if (s > bv) { bv = s; bi = i; }
+        if (arg_beats(s, i, bv, bi)) { bv = s; bi = i; }
     }
     block_argmax(bv, bi, r);                                     // syncs: Ms visible to the block
-    const int64_t center = bi;
+    const int64_t center = bi;                                   // in [0, Lo): Lo >= 1 here
     const double mcen = Ms[center];
     int64_t res = NONE;
     int32_t br = 0;
@@ -201,7 +219,7 @@ __global__ __launch_bounds__(PW) void plateau_kernel(PlArgs a) {
     // (c) right edge of the earliest run of length >= max(8, cp/2) above 60 % (sc.py:117-133)
     if (res == NONE) {
         const int64_t min_run = max((int64_t)8, (int64_t)(a.cp / 2));
-        const double peak = mcen;                                // == max(Ms)
+        const double peak = mcen;                                // == np.max(Ms), NaN included
         if (peak > 0) {
             const double thr = 0.6 * peak;
             int64_t best = NONE, best_end = 0;
@@ -238,9 +256,9 @@ __global__ __launch_bounds__(PW) void plateau_kernel(PlArgs a) {
             for (int64_t k = t; k < nd; k += PW) {
                 const double wv = Ms[ws + (nw == 1 ? 0 : k)], av = Ms[as + (na == 1 ? 0 : k)];
                 const double d = wv - av;
-                if (d > dv) { dv = d; di = k; }
+                if (arg_beats(d, k, dv, di)) { dv = d; di = k; }
             }
-            block_argmax(dv, di, r);
+            block_argmax(dv, di, r);                             // nd >= 1: di in [0, nd)
             res = lo + di + L / 2; br = 3;
         }
     }
@@ -266,10 +284,10 @@ __global__ __launch_bounds__(PW) void minn_peak_kernel(const double* Ms_all, int
     double mv = -INFINITY;
     int64_t mi = NONE;
     for (int64_t i = t; i < n; i += PW)
-        if (Ms[i] > mv) { mv = Ms[i]; mi = i; }
-    block_argmax(mv, mi, r);
-    if (!(mv > 0.0)) { put(-1, 0, 0, -2); return; }            // minn.py:151-153
-    const double level = thr * mv;                              // :154
+        if (arg_beats(Ms[i], i, mv, mi)) { mv = Ms[i]; mi = i; }
+    block_argmax(mv, mi, r);                                    // mv == np.max(Ms), mi == np.argmax(Ms)
+    if (mv <= 0.0) { put(-1, 0, 0, -2); return; }               // minn.py:151-153 (a NaN maximum goes on)
+    const double level = thr * mv;                              // :154 (NaN: no sample passes)
     int64_t bl = 0, bs = NONE;                                  // longest run, earliest start
     for_each_run(0, n, [&](int64_t j) { return Ms[j] >= level; },
                  [&](int64_t s, int64_t e) { if (e - s > bl || (e - s == bl && s < bs)) { bl = e - s; bs = s; } }, r);
@@ -284,8 +302,8 @@ __global__ __launch_bounds__(PW) void minn_peak_kernel(const double* Ms_all, int
     double pv = -INFINITY;
     int64_t pi = NONE;
     for (int64_t i = s + t; i < e; i += PW)
-        if (Ms[i] > pv) { pv = Ms[i]; pi = i; }
-    block_argmax(pv, pi, r);                                                    // :202-205
+        if (arg_beats(Ms[i], i, pv, pi)) { pv = Ms[i]; pi = i; }
+    block_argmax(pv, pi, r);                                                    // :202-205, s < e
     put(pi, s, e, 0);
 }
 
@@ -305,13 +323,13 @@ __global__ __launch_bounds__(PW) void sc_gate_kernel(const T* M_all, int64_t n, 
     int64_t mi = NONE;
     for (int64_t i = t; i < n; i += PW) {
         const double v = ld(M, i);
-        if (v > mv) { mv = v; mi = i; }
+        if (arg_beats(v, i, mv, mi)) { mv = v; mi = i; }
     }
-    block_argmax(mv, mi, r);
+    block_argmax(mv, mi, r);                                     // np.max / np.argmax: mi < n when n > 0
     int64_t first = NONE, last = -1;
     for (int64_t i = t; i < n; i += PW) {
         const double v = ld(M, i);
-        const bool g = mv > 0 ? (v / mv >= thr) : (v >= thr);
+        const bool g = mv > 0 ? (v / mv >= thr) : (v >= thr);    // a NaN maximum: unnormalised
         if (mask) mask[i] = g;
         if (g) { first = min(first, i); last = max(last, i); }
     }
@@ -345,12 +363,18 @@ __global__ __launch_bounds__(PW) void segment_peak_kernel(const double* Ms_all, 
     for (int64_t i = s + t; i < bhi; i += PW)
         if (!mask[i]) { e = i; break; }
     e = min(block_min(e, r), bhi);
+    // The reference's loop (combined_sc_min.py:195-203): best = Ms[s], then strict > over the
+    // rest.  A NaN seed is never beaten; otherwise no NaN ever becomes the best value, so the
+    // answer is the first maximum of the run's non-NaN samples (s among them, -inf included).
+    const double seed = Ms[s];
     double pv = -INFINITY;
     int64_t pi = NONE;
-    for (int64_t i = s + t; i < e; i += PW)
-        if (Ms[i] > pv) { pv = Ms[i]; pi = i; }
+    for (int64_t i = s + t; i < e; i += PW) {
+        const double v = Ms[i];
+        if (v == v && arg_beats(v, i, pv, pi)) { pv = v; pi = i; }
+    }
     block_argmax(pv, pi, r);
-    if (t == 0) { peak[b] = pi; status[b] = 0; }
+    if (t == 0) { peak[b] = seed != seed ? s : pi; status[b] = 0; }
 }
 
 bool real_ok(int p) { return p == OFS_FP32 || p == OFS_FP64; }

@@ -26,6 +26,9 @@ Reference entry points exercised (file:line into /root/reference):
   zc_v2.matched_filter_correlation / normalize_correlation / zc_streaming_detection /
   detect_zc_peaks / detect_zc_preamble zc_v2.py:244-519
   zc.py:106-126 inline combined matched filter (restated in gen_zc from the reference's lines)
+  sc.find_plateau_end_from_metric / minn.find_minn_peak / combined_sc_min.find_minn_peak,
+  _streaming_peak_detector and the gate inside run_simulation, on the exact tie and non-finite
+  streams of tests/post_streams.py (gen_post_exact)
 Input builders used only to synthesise realistic streams (not part of the parity surface):
   sync_aa.build_aa_preamble / apply_channel_multi_antenna / apply_cfo / quantize_adc,
   sc.build_sc_preamble, combined_sc_min.build_minn_preamble, minn_rtl.build_minn_preamble_generic,
@@ -508,6 +511,148 @@ def gen_post(R, cases):
     cases["post_streaming_peak"] = dict(kind="streaming_peak", metric=met, peak_bounded=np.int64(pk_b), **sp)
 
 
+class _GateCaptured(Exception):
+    pass
+
+
+def _reference_gate(comb, M_sc, M_minn, thr):
+    """The gate of combined_sc_min.run_simulation (combined_sc_min.py:337-358) as the reference's own
+    statements compute it: run_simulation with its two metric functions replaced by ones that hand back
+    M_minn and M_sc, SC_GATE_THRESHOLD set to thr, and find_minn_peak replaced by a hook that keeps the
+    gate mask it is given (:360-365) and ends the run before any plot."""
+    seen = {}
+
+    def hook(M, smooth_win=8, gate_mask=None, search_bounds=None):
+        seen["gate"] = np.array(gate_mask, bool)
+        raise _GateCaptured
+
+    saved = (comb.minn_streaming_metric, comb.schmidl_cox_streaming_metric, comb.find_minn_peak,
+             comb.SC_GATE_THRESHOLD)
+    comb.minn_streaming_metric = lambda rx: (np.array(M_minn), None, None)
+    comb.schmidl_cox_streaming_metric = lambda rx: (np.array(M_sc), None, None)
+    comb.find_minn_peak, comb.SC_GATE_THRESHOLD = hook, thr
+    try:
+        with np.errstate(all="ignore"):
+            comb.run_simulation(None, "post_exact")
+    except _GateCaptured:
+        pass
+    finally:
+        (comb.minn_streaming_metric, comb.schmidl_cox_streaming_metric, comb.find_minn_peak,
+         comb.SC_GATE_THRESHOLD) = saved
+    gate = seen["gate"]
+    first, last = int(np.argmax(gate)), int(gate.size - np.argmax(gate[::-1]) - 1)   # :353-355
+    return gate, (first, last + 1)
+
+
+def gen_post_exact(R, cases):
+    """The reference's own decisions on exact tie and non-finite streams (tests/post_streams.py, lengths 9
+    and 257): the whole non-finite family, every stream of the level, gate and segment families and the tie
+    streams of the metric pool, under a subset of the parameter sets.  One file per entry point and
+    length, kind "post_exact": the unique streams once (data_*), and per record the stream's row, the
+    parameters (None as -1 / has_bounds 0) and what sc.find_plateau_end_from_metric, minn.find_minn_peak,
+    combined_sc_min._streaming_peak_detector, combined_sc_min.find_minn_peak and the gate of
+    run_simulation returned; error 1 = ValueError."""
+    here = Path(__file__).resolve().parent
+    for p_ in (here.parent, here.parent.parent / "oracle"):
+        if str(p_) not in sys.path:
+            sys.path.insert(0, str(p_))
+    import post_streams as S
+    sc, minn, comb = R["sc"], R["minn"], R["combined"]
+    keep = {"zeros", "flat", "tie+1", "tie+64", "tie_ends", "two_runs", "saw", "peak_last", "all_hi"}
+
+    def wanted(c):
+        p = c.params
+        if c.op == "plateau":
+            return c.family in ("p95", "p60") or (p[2] in (1, 8) and p[0] in (0, 16, 64) and p[1] != 3)
+        if c.op == "minn":
+            return p[0] in (1, 8) and p[1] == 0.5 and p[2] in S.bounds_set(c.n)[:2]
+        if c.op == "seg":                                    # bounds exist only in find_minn_peak (the detect cases)
+            return p[0] is None
+        return c.op in ("gate", "detect")
+
+    def picked(c):
+        if c.family != "metric":
+            return list(range(len(c.names)))
+        return [b for b, nm in enumerate(c.names) if nm.startswith("edge_") or set(nm.split("|")) <= keep]
+
+    for n in (9, 257):
+        recs = {}                                            # op -> lists
+        for c in S.cases(n):
+            if c.op == "trail" or not wanted(c):
+                continue
+            for b in picked(c):
+                recs.setdefault(c.op, []).append((c, b))
+        for op, lst in recs.items():
+            keys = list(lst[0][0].data)
+            uniq = {k: {} for k in keys}                     # bytes of a row -> its index in data_k
+            rowsk = {k: [] for k in keys}
+            names, par, res = [], [], {}
+
+            def row_of(k, a):
+                key = a.tobytes()
+                if key not in uniq[k]:
+                    uniq[k][key] = len(rowsk[k])
+                    rowsk[k].append(np.array(a))
+                return uniq[k][key]
+
+            def out(**kw):
+                for k_, v in kw.items():
+                    res.setdefault(k_, []).append(v)
+
+            ms_rows, ms_key = [], {}
+            for c, b in lst:
+                p = c.params
+                arrs = [np.array(c.data[k][b]) for k in keys]
+                names.append(f"{c.family}:{c.names[b]}")
+                out(**{f"row_{k}": row_of(k, a) for k, a in zip(keys, arrs)})
+                with np.errstate(all="ignore"):
+                    if op == "plateau":
+                        par.append([p[0], -1 if p[1] is None else p[1], p[2]])
+                        try:
+                            out(index=int(sc.find_plateau_end_from_metric(arrs[0], p[0], lookahead=p[1], smooth_win=p[2])),
+                                error=0)
+                        except ValueError:
+                            out(index=-1, error=1)
+                    elif op == "minn":
+                        bd = p[2]
+                        par.append([p[0], p[1], bd is not None, *(bd or (0, 0))])
+                        try:
+                            pk, gate, Ms = minn.find_minn_peak(arrs[0], smooth_win=p[0], gate_threshold=p[1], search_bounds=bd)
+                            idx = np.flatnonzero(gate)
+                            assert idx.size == idx[-1] - idx[0] + 1          # one run: stored as [lo, hi)
+                            k2 = (res["row_M"][-1], p[0])
+                            if k2 not in ms_key:
+                                ms_key[k2] = len(ms_rows)
+                                ms_rows.append(np.asarray(Ms, float))
+                            assert np.array_equal(ms_rows[ms_key[k2]], Ms, equal_nan=True)
+                            out(peak=int(pk), gate_lo=int(idx[0]), gate_hi=int(idx[-1]) + 1, ms_row=ms_key[k2], error=0)
+                        except ValueError:
+                            out(peak=-1, gate_lo=0, gate_hi=0, ms_row=-1, error=1)
+                    elif op == "gate":
+                        par.append([p[0]])
+                        gate, span = _reference_gate(comb, arrs[0], np.zeros(n), p[0])
+                        out(gate=gate, first=span[0], last1=span[1])
+                    elif op == "seg":
+                        par.append([0])
+                        r = comb._streaming_peak_detector(arrs[0], arrs[1])
+                        out(peak=-1 if r is None else int(r))
+                    else:
+                        bd = p[2]
+                        par.append([p[0], p[1], bd is not None, *(bd or (0, 0))])
+                        gate, span = _reference_gate(comb, arrs[1], arrs[0], p[1])
+                        try:
+                            out(peak=int(comb.find_minn_peak(arrs[0], smooth_win=p[0], gate_mask=gate, search_bounds=bd)),
+                                error=0, first=span[0], last1=span[1])
+                        except ValueError:
+                            out(peak=-1, error=1, first=span[0], last1=span[1])
+            d = dict(kind="post_exact", op=op, n=np.int64(n), names=np.array(names),
+                     params=np.array(par, np.float64), **{f"data_{k}": np.array(rowsk[k]) for k in keys},
+                     **{k_: np.array(v) for k_, v in res.items()})
+            if op == "minn":
+                d["Ms"] = np.array(ms_rows, np.float64).reshape(len(ms_rows), n)
+            cases[f"post_exact_{op}_n{n}"] = d
+
+
 def gen_synth(R, cases):
     """Input builders the GPU synthesis restates (synth.py / synth.hip): the measured CIR banks
     (channel.load_measured_cir, channel.py:15-48), the [A][A] preambles (sync_aa.build_aa_preamble,
@@ -550,6 +695,7 @@ def main():
     gen_park(R, cases)
     gen_zc(R, cases)
     gen_post(R, cases)
+    gen_post_exact(R, cases)
     gen_synth(R, cases)
     OUT.mkdir(parents=True, exist_ok=True)
     only = set(sys.argv[1:])               # optional case names: rewrite only those files

@@ -181,6 +181,49 @@ def test_oracle_matches_reference_golden(path):
         for j in range(4):
             r = O.streaming_peak(d["metric"], d[f"mask{j}"])
             assert (-1 if r is None else r) == int(d[f"peak{j}"])
+    elif kind == "post_exact":
+        # the reference's own decisions on the exact tie and non-finite streams of tests/post_streams.py
+        op, par, names = str(d["op"]), d["params"], d["names"]
+        bnd = lambda p: (int(p[-2]), int(p[-1])) if p[-3] else None   # noqa: E731
+        assert len(names) == len(par) > 0
+        with np.errstate(all="ignore"):
+            for k, p in enumerate(par):
+                t = (op, str(names[k]), p.tolist())
+                if op == "plateau":
+                    M, la = d["data_M"][d["row_M"][k]], None if p[1] < 0 else int(p[1])
+                    if d["error"][k]:
+                        with pytest.raises(ValueError):
+                            O.plateau_end(M, int(p[0]), la, int(p[2]))
+                    else:
+                        assert O.plateau_end(M, int(p[0]), la, int(p[2]))[0] == d["index"][k], t
+                elif op == "minn":
+                    M = d["data_M"][d["row_M"][k]]
+                    if d["error"][k]:
+                        with pytest.raises(ValueError):
+                            O.minn_peak(M, int(p[0]), float(p[1]), bnd(p))
+                    else:
+                        pk, gate, Ms = O.minn_peak(M, int(p[0]), float(p[1]), bnd(p))
+                        want = np.zeros(M.size, bool)
+                        want[d["gate_lo"][k]:d["gate_hi"][k]] = True
+                        assert pk == d["peak"][k] and np.array_equal(gate, want), t
+                        assert np.array_equal(Ms, d["Ms"][d["ms_row"][k]], equal_nan=True), t
+                elif op == "gate":
+                    mask, span = O.sc_gate(d["data_M"][d["row_M"][k]], float(p[0]))
+                    assert np.array_equal(mask, d["gate"][k]) and span == (d["first"][k], d["last1"][k]), t
+                elif op == "seg":
+                    r = O.streaming_peak(d["data_Ms"][d["row_Ms"][k]], d["data_mask"][d["row_mask"][k]])
+                    assert (-1 if r is None else r) == d["peak"][k], t
+                elif op == "detect":
+                    Mm, Msc = d["data_M_minn"][d["row_M_minn"][k]], d["data_M_sc"][d["row_M_sc"][k]]
+                    mask, span = O.sc_gate(Msc, float(p[1]))
+                    assert span == (d["first"][k], d["last1"][k]), t
+                    if d["error"][k]:
+                        with pytest.raises(ValueError):
+                            O.comb_minn_peak(Mm, int(p[0]), mask, bnd(p))
+                    else:
+                        assert O.comb_minn_peak(Mm, int(p[0]), mask, bnd(p)) == d["peak"][k], t
+                else:
+                    pytest.fail(op)
     elif kind == "synth":
         pass        # input builders of the synthesis: pinned in tests/test_host_logic.py
     else:
