@@ -105,6 +105,8 @@ const char* ofs_status_string(int32_t status);
  *   FAST_RMPAIR  0|1: R and M of two adjacent rows of the one-antenna E = 2 storing aa_fast kernel as
  *                one 16-byte store per lane (one contiguous 1 KiB span per wave instruction; default 1)
  *   FAST_ST_POLICY 0|1: that kernel's P/R/M stores plain / non-temporal (default 1)
+ *   FAST_LD_POLICY 0: input loads of that kernel's full-stream form plain instead of non-temporal (same
+ *                bits; default 1, any other value is the default; A/B and the tests' reference arm)
  *   FAST_HEAD    0: ofs_aa_detect_ex ignores OFS_AA_HEAD_RESIDENT (the P/M head is rewritten; A/B of
  *                both arms on the same buffers)
  *   FAST_FULL    0: the headline shape (one antenna, T = 1024, L = 128 | 256 | 512, P, R, M and events,

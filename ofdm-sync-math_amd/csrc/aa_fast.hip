@@ -59,6 +59,19 @@ __device__ __forceinline__ void st_out(float2* p, float2 v) {
     else *p = v;
 }
 
+// Input loads of the full-stream form: 16 bytes at p.  LP = cache policy (variant FAST_LD_POLICY): 0 plain,
+// 1 non-temporal (the default, launch(): x is read exactly once).  Both are loads whose returns the compiler
+// counts itself (the per-row vmcnt waits depend on it).
+template <int LP>
+__device__ __forceinline__ float4 ld_x(const char* p) {
+    if constexpr (LP == 1) {
+        const nf4 v = __builtin_nontemporal_load(reinterpret_cast<const nf4*>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+        return *reinterpret_cast<const float4*>(p);
+    }
+}
+
 // Row-paired R / M store (E = 2): rows k, k+1 of one stream are 256 consecutive floats (1 KiB) of the
 // buffer.  Lane l holds (a[0], a[1]) = floats 2l, 2l+1 of row k and (b[0], b[1]) of row k+1; it stores
 // floats [4l, 4l+4) of the span - the values of lanes 2(l & 31), 2(l & 31) + 1 of row k + (l >= 32) -
@@ -106,10 +119,12 @@ __device__ __forceinline__ void st_rows2(float* span, const float (&a)[2], const
 // the paired R/M spans alike; the row offset is a constant), the above flags are an fp32 compare against
 // AaFastArgs::thr32, and the gate machine is chosen at launch: FS = 1 the scan-free rows (max(hyst, 1)
 // >= RL), FS = 2 the scan rows - not both bodies inline behind a per-row test.
-template <int E, int MR, int NA, bool DO, bool S32, int SV = 0, int FS = 0>
+// LP: cache policy of the full-stream form's input loads (ld_x)
+template <int E, int MR, int NA, bool DO, bool S32, int SV = 0, int FS = 0, int LP = 0>
 __global__ __launch_bounds__(FAST_WG) void aa_fast_kernel(AaFastArgs a) {
     static_assert(SV == 0 || (E == 2 && NA == 1 && !DO), "store-path variants: one-antenna E = 2 storing kernel");
     static_assert(FS == 0 || (SV == 3 && !S32), "full-stream form: the headline's kernel");
+    static_assert(LP == 0 || FS != 0, "load-policy arms: the full-stream form");
     constexpr bool FULL = FS != 0;
     constexpr int SP = SV & 1;                 // output store cache policy
     constexpr bool RP = (SV & 2) != 0;         // R/M of rows k, k+1 (k even) as one 16-byte store per lane
@@ -139,7 +154,7 @@ __global__ __launch_bounds__(FAST_WG) void aa_fast_kernel(AaFastArgs a) {
     if constexpr (FULL) {
         const char* const xb = reinterpret_cast<const char*>(a.x) + b * (TMAX * 8);
 #pragma unroll
-        for (int k = 0; k < RW; ++k) xreg[0][k][0] = *reinterpret_cast<const float4*>(xb + RL * 8 * k + lo16);
+        for (int k = 0; k < RW; ++k) xreg[0][k][0] = ld_x<LP>(xb + RL * 8 * k + lo16);
     } else {
 #pragma unroll
         for (int t = 0; t < NA; ++t) {
@@ -686,10 +701,17 @@ int launch(const AaFastArgs& a, hipStream_t st) {
                     // 0.205-0.213 ms) - both beat the generic form's 0.220-0.226 ms.  DESIGN.md §4.1.
                     const int64_t padf = ofs::variant_or(ofs::V_FAST_LDS, FAST_CAP_LDS_FULL);
                     const size_t shmf = padf > 0 && padf <= 65536 ? (size_t)padf : 0;
-                    if ((a.hyst > 1 ? a.hyst : 1) >= 64 * E)
-                        hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 1>), grid, blk, shmf, st, f);
-                    else
-                        hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 2>), grid, blk, shmf, st, f);
+                    const bool ff = (a.hyst > 1 ? a.hyst : 1) >= 64 * E;
+                    // Input loads non-temporal (ld_x; variant FAST_LD_POLICY = 0: plain, the tests' reference arm;
+                    // any other value is the default).  Paired on the same buffers against plain loads, 3 fresh
+                    // allocations x 11 rotated repetitions: -4.4..-6.3 %; the raw-buffer-load forms measured with
+                    // it (plain, sc1, sc0 sc1 within +-0.5 % of the plain global load, nt = this arm) were removed.
+                    // The cap was re-swept under it and stays at 7 per CU.  DESIGN.md §4.1.
+                    const bool nt = ofs::variant(ofs::V_FAST_LD_POLICY) != 0;
+                    if (ff && nt) hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 1, 1>), grid, blk, shmf, st, f);
+                    else if (ff) hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 1, 0>), grid, blk, shmf, st, f);
+                    else if (nt) hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 2, 1>), grid, blk, shmf, st, f);
+                    else hipLaunchKernelGGL((aa_fast_kernel<E, MR, NA, false, false, 3, 2, 0>), grid, blk, shmf, st, f);
                     return hipGetLastError() == hipSuccess ? 1 : OFS_EHIP;
                 }
             }
