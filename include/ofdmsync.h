@@ -411,6 +411,66 @@ int32_t ofs_win_plan(int32_t kind, int32_t in_fmt, int32_t precision, int32_t n_
                      int32_t symbol_len);
 
 /*
+ * Resumable chunked S&C / combined S&C / Minn window metrics for complex64 streams: the chunk-fed form
+ * of the streaming fp32 fast kernel behind ofs_sc_metric / ofs_minn_metric (ofs_win_plan > 0).  The
+ * reference's sc.sc_streaming_metric, combined_sc_min.schmidl_cox_streaming_metric and
+ * minn.minn_streaming_metric(_parameterized) are the specification.
+ *
+ * A stream is fed in consecutive chunks of Tc samples; ofs_win_metric_chunk returns M, P, R at the
+ * chunk's samples and keeps what the next call needs (the last 1.5 N samples at most, and the fp64 row
+ * bases of the one-shot kernel) in a caller-owned state buffer on the device.  The library allocates
+ * nothing and keeps no global state.
+ *   kind    1 = ofs_sc_metric r_mode 0, 2 = ofs_sc_metric r_mode 1, 3 = ofs_minn_metric (as ofs_win_plan;
+ *           kind 4, the fused kernel, has no chunked form).
+ *   x       [B][n_br][Tc] complex64 (this call's chunk), branches summed.  Supported (kind, n_br,
+ *           symbol_len) are exactly those with ofs_win_plan(kind, OFS_C64, OFS_FP32, n_br, T, symbol_len) > 0
+ *           for some T >= symbol_len: n_br 1-2, the window W = symbol_len / 2 (kinds 1, 2) or
+ *           symbol_len / 4 (kind 3) one of 128, 256, 512, 1024, 2048, and W = 2048 with one branch only.
+ *   state   [B][ofs_win_chunk_state_bytes(kind, n_br, symbol_len)] bytes, 16-byte aligned, device memory.
+ *           The layout is opaque; ALL-ZERO BYTES ARE A FRESH STREAM, so any subset of streams is reset
+ *           with a memset of its rows (stream-ordered with the calls).  One state row belongs to one
+ *           stream: kind, n_br and symbol_len must not change between the calls of a stream, and the
+ *           calls of a stream must be ordered (same HIP stream, or synchronised by the caller).
+ *   M, P, R [B][Tc] f32 / c64 / f32, EACH nullable.  Element i of a call belongs to the stream's newest
+ *           sample n = (samples of earlier calls) + i, that is to the reference's output index
+ *           d = n - (symbol_len - 1).  Elements with d < 0 are written as +0.0 (all-zero bits) for any
+ *           input, NaN and Inf included.  The fill phase is decided per stream on n, so after a reset of
+ *           some state rows the streams of one call may be at different n.
+ *   d0      [B] int64, nullable; every call writes the d of its element 0 (negative while a stream fills).
+ *   final   != 0 changes nothing in the outputs; the state is a fresh stream again after the call.
+ *   Tc      1 .. ofs_win_chunk_max_samples(kind, n_br, symbol_len) = 2^30 (in-call positions - at most
+ *           1.5 * symbol_len + 255 history samples, the chunk and one row of padding - stay below
+ *           2^31); Tc = 0 with final != 0 is a flush: no samples, d0 written, the streams fresh afterwards
+ *           (x and the arrays unused).
+ * EQUIVALENCE GUARANTEE.  For any split of a stream of T >= symbol_len samples into chunks, each output
+ * array concatenated over the calls, with its first symbol_len - 1 elements dropped, equals BIT FOR BIT
+ * the [T - symbol_len + 1] array that ONE ofs_sc_metric (kinds 1, 2) or ofs_minn_metric (kind 3) call with
+ * OFS_C64 and OFS_FP32 returns on the whole stream on its fast plan - whichever of M / P / R are
+ * requested here.  Exception: behind non-finite samples an output word is a NaN exactly where the
+ * one-shot call's is, with the same payload, but its SIGN bit is outside the guarantee (as for
+ * ofs_aa_detect_chunk_f32).
+ * STREAM LENGTH.  The state carries the fp64 running sums C of the row totals since sample 0 (of the
+ * lagged products and of the energy), and a window's "rows between" term is a difference of two of
+ * them, so its absolute error grows as 2^-53 * |C|.  At unit amplitude |C| is about the sample count n,
+ * and a window sum is about W with an fp32 ulp of 2^-23 * W: the carried error reaches one such ulp at
+ * n = 2^30 * W samples (2^37 for W = 128, 2^41 for W = 2048: hours at 100 MS/s).  Up to there the
+ * guarantee above is what bounds the error (it is the one-shot call's); beyond it the outputs still
+ * equal what a one-shot call of that length would compute, but that value itself degrades.  final (or
+ * zeroing the state) restarts C.  Energy far above unit amplitude shortens the span in proportion.
+ * Calls are stream-ordered and never synchronise with the host: consecutive chunks may be enqueued back
+ * to back.  OFS_EINVAL (before any launch): an unsupported (kind, n_br, symbol_len), Tc < 0 or above the
+ * limit, Tc = 0 without final, B < 0, a null or misaligned state with B > 0, a null x with B * Tc > 0.
+ * B = 0 is a valid no-op.  There is no fall-back to the general engine.  ofs_win_chunk_state_bytes
+ * returns the bytes of ONE stream's state (a multiple of 16) and ofs_win_chunk_max_samples the largest
+ * Tc of one call; both return OFS_EINVAL (< 0) for an unsupported shape.
+ */
+int64_t ofs_win_chunk_state_bytes(int32_t kind, int32_t n_br, int32_t symbol_len);
+int64_t ofs_win_chunk_max_samples(int32_t kind, int32_t n_br, int32_t symbol_len);
+int32_t ofs_win_metric_chunk(int32_t kind, const void* x, int64_t B, int32_t n_br, int64_t Tc,
+                             int32_t symbol_len, void* state, void* M, void* P, void* R,
+                             int64_t* d0, int32_t final, void* stream);
+
+/*
  * CP-correlation CFO: replaces core.estimate_cfo_from_cp (core.py:179-196), batched with a
  * per-stream CP start.  starts: [B] int64 (device); P_out: [B][2] f64 (nullable);
  * cfo_out: [B] f64.  Windows must lie inside [0, T) (checked by the caller).

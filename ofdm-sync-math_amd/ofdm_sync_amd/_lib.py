@@ -120,6 +120,10 @@ def _declare(lib):
         "ofs_sc_minn_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, P, P,
                                          P, P, P, P, P]),
         "ofs_win_plan": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int32]),
+        "ofs_win_chunk_state_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+        "ofs_win_chunk_max_samples": (c_int64, [c_int32, c_int32, c_int32]),
+        "ofs_win_metric_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, P, P, P, P, P,
+                                           c_int32, P]),
         "ofs_rtl_plan": (c_int32, [c_int32, c_int32, c_int64, c_int32]),
         "ofs_trailing_average": (c_int32, [c_int32, P, c_int64, c_int64, c_int32, c_int32, P, P]),
         "ofs_plateau_end": (c_int32, [c_int32, P, c_int64, c_int64, c_int32, c_int32, c_int32, P, P, P,

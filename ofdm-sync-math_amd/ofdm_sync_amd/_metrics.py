@@ -63,3 +63,147 @@ def window_metric(kind: str, x, N: int, *, batched: bool, precision=None):
         return (_lib.to_host(M[0], np.float64), _lib.to_host(P[0], np.complex128),
                 _lib.to_host(R[0], np.float64))
     return M[0], P[0], R[0]
+
+
+# ---- resumable chunked form (csrc/win_chunk.hip, ofs_win_metric_chunk) -------------------------
+KINDS = {_SC: 1, _COMB: 2, _MINN: 3, 1: 1, 2: 2, 3: 3}        # ofs_win_plan kinds
+
+
+class WindowChunkResult:
+    """Outputs of one ``WindowMetricChunked.push``: ``M`` float32, ``P`` complex64, ``R`` float32, each
+    ``[B, Tc]`` or None when not requested, and ``d0`` ``[B]`` int64, the reference's output index d of
+    element 0 (element i belongs to d0 + i; negative while a stream fills, those elements are +0.0)."""
+    __slots__ = ("M", "P", "R", "d0")
+
+    def __init__(self, M, P, R, d0):
+        self.M, self.P, self.R, self.d0 = M, P, R, d0
+
+
+class WindowMetricChunked:
+    """Resumable S&C / combined S&C / Minn timing metric over B complex64 streams that arrive in chunks
+    (``ofs_win_metric_chunk``).
+
+    The chunk-fed form of the streaming fp32 fast path behind ``window_metric``.  ``kind`` is "sc",
+    "comb" or "minn" (or 1, 2, 3 as in ``ofs_win_plan``).  ``push(x)`` takes the next ``Tc`` samples of
+    every stream - complex64 ``[B, n_branch, Tc]``, or ``[B, Tc]`` for one branch - and returns M / P / R
+    ``[B, Tc]`` at those samples: element i belongs to the stream's newest sample n = samples_seen + i,
+    that is to the reference's output index d = n - (symbol_len - 1); ``d0`` holds the d of element 0 and
+    elements with d < 0 are +0.0.  Interface and buffer ownership are those of
+    ``sync_aa.AAChunkedDetectorF32``: ``push(x, final=True)`` or ``flush()`` leaves fresh streams, the
+    result buffers are this object's (cached per ``Tc``, overwritten in stream order by a later ``push``
+    of that length), ``push`` enqueues one launch and never synchronises.
+
+    For any chunking of a stream of T >= symbol_len samples, the concatenated outputs with their first
+    symbol_len - 1 elements dropped equal, bit for bit, the one-shot batched call on the whole complex64
+    stream (fp32, ``ofs_win_plan`` > 0) - whichever outputs are requested.  The state carries the fp64
+    running row sums since sample 0: at unit amplitude their rounding reaches one fp32 ulp of a window
+    sum after about ``2**30 * W`` samples (include/ofdmsync.h); a final call restarts them.
+    The window W (symbol_len / 2, Minn: symbol_len / 4) is 128, 256, 512, 1024 or 2048 (2048: one
+    branch); kind, n_branch and symbol_len are fixed for the object's life.
+    """
+
+    def __init__(self, kind, B: int, n_branch: int = 1, symbol_len: int = 2048,
+                 outputs=("M", "P", "R"), device=None):
+        if kind not in KINDS:
+            raise ValueError(f"kind must be 'sc', 'comb' or 'minn' (or 1, 2, 3), got {kind!r}")
+        dev = torch.device(device) if device is not None else _lib.require_gpu()
+        lib = _lib.lib()
+        self.kind = KINDS[kind]
+        nbytes = int(lib.ofs_win_chunk_state_bytes(self.kind, int(n_branch), int(symbol_len)))
+        if nbytes < 0 or B < 0:
+            raise ValueError(f"WindowMetricChunked supports 1-2 branches and a window (symbol_len / 2, Minn: "
+                             f"symbol_len / 4) of 128/256/512/1024/2048, 2048 with one branch "
+                             f"(got kind={kind!r}, n_branch={n_branch}, symbol_len={symbol_len}, B={B})")
+        bad = [o for o in outputs if o not in ("M", "P", "R")]
+        if bad:
+            raise ValueError(f"outputs may name 'M', 'P' and 'R', got {bad}")
+        self.B, self.n_branch, self.symbol_len, self.device = int(B), int(n_branch), int(symbol_len), dev
+        self.max_chunk = int(lib.ofs_win_chunk_max_samples(self.kind, self.n_branch, self.symbol_len))
+        self.outputs = tuple(outputs)
+        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
+        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
+        self._fn = lib.ofs_win_metric_chunk
+        self._bufs: dict[int, WindowChunkResult] = {}
+
+    def _buffers(self, Tc: int) -> WindowChunkResult:
+        r = self._bufs.get(Tc)
+        if r is None:
+            B, dev, want = self.B, self.device, self.outputs
+            M = torch.empty((B, Tc), dtype=torch.float32, device=dev) if "M" in want and Tc else None
+            P = torch.empty((B, Tc), dtype=torch.complex64, device=dev) if "P" in want and Tc else None
+            R = torch.empty((B, Tc), dtype=torch.float32, device=dev) if "R" in want and Tc else None
+            r = self._bufs[Tc] = WindowChunkResult(M, P, R, torch.zeros((B,), dtype=torch.int64, device=dev))
+        return r
+
+    def _call(self, x, Tc: int, final: bool) -> WindowChunkResult:
+        r = self._buffers(Tc)
+        rc = self._fn(self.kind, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.symbol_len,
+                      self.state.data_ptr(), _lib.ptr(r.M), _lib.ptr(r.P), _lib.ptr(r.R), r.d0.data_ptr(),
+                      int(bool(final)), _lib.stream_ptr())
+        _lib.check(rc, "ofs_win_metric_chunk")
+        self.samples_seen = 0 if final else self.samples_seen + Tc
+        return r
+
+    def _chunk(self, x, final: bool):
+        """Validate one chunk (before any library call): the contiguous device tensor and its Tc."""
+        what = (f"[{self.B}, {self.n_branch}, Tc] complex64" +
+                (f" (or [{self.B}, Tc])" if self.n_branch == 1 else ""))
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.complex64:
+            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
+        if x.dim() == 2 and self.n_branch == 1:
+            x = x[:, None, :]
+        if x.dim() != 3 or x.shape[0] != self.B or x.shape[1] != self.n_branch:
+            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
+        Tc = int(x.shape[2])
+        if Tc > self.max_chunk:
+            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
+        if Tc == 0 and not final:
+            raise ValueError("an empty chunk is only valid with final=True (or flush())")
+        if x.device != self.device:
+            x = x.to(self.device)
+        return x.contiguous(), Tc
+
+    def push(self, x: torch.Tensor, final: bool = False) -> WindowChunkResult:
+        """The next chunk of every stream; ``final=True`` also ends the streams (fresh afterwards)."""
+        x, Tc = self._chunk(x, final)
+        return self._call(x, Tc, final)
+
+    def flush(self) -> WindowChunkResult:
+        """End the streams without new samples (M, P, R are None); the streams are fresh afterwards."""
+        return self._call(None, 0, True)
+
+    def reset(self, mask: torch.Tensor | None = None) -> None:
+        """Make all streams fresh, or those where ``mask`` [B] (bool) is set (stream-ordered, no
+        synchronisation).  ``samples_seen`` restarts only on a full reset."""
+        if mask is None:
+            self.state.zero_()
+            self.samples_seen = 0
+        else:
+            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
+            self.state.masked_fill_(m[:, None], 0)
+
+
+class SCMinnChunked:
+    """Combined S&C (kind 2) and Minn (kind 3) on the same chunks, two launches per ``push``: returns
+    ``(minn, sc)`` results, each as ``WindowMetricChunked`` returns them.  The yardsticks are the two
+    separate one-shot calls (not the fused ``ofs_sc_minn_metric``, whose S&C energy rounds differently)."""
+
+    def __init__(self, B: int, n_branch: int = 1, symbol_len: int = 2048, outputs=("M", "P", "R"), device=None):
+        self.minn = WindowMetricChunked(_MINN, B, n_branch, symbol_len, outputs=outputs, device=device)
+        self.sc = WindowMetricChunked(_COMB, B, n_branch, symbol_len, outputs=outputs, device=device)
+        self.max_chunk = min(self.minn.max_chunk, self.sc.max_chunk)
+
+    @property
+    def samples_seen(self) -> int:
+        return self.sc.samples_seen
+
+    def push(self, x: torch.Tensor, final: bool = False):
+        x, Tc = self.sc._chunk(x, final)
+        return self.minn._call(x, Tc, final), self.sc._call(x, Tc, final)
+
+    def flush(self):
+        return self.minn.flush(), self.sc.flush()
+
+    def reset(self, mask: torch.Tensor | None = None) -> None:
+        self.minn.reset(mask)
+        self.sc.reset(mask)

@@ -6,7 +6,7 @@ Both run on the HIP window-metric engine (``ofs_minn_metric`` / ``ofs_sc_metric`
 """
 from __future__ import annotations
 
-from ._metrics import window_metric
+from ._metrics import SCMinnChunked, WindowMetricChunked, window_metric
 
 N_FFT = 2048            # core.py:6
 SC_GATE_THRESHOLD = 0.6  # combined_sc_min.py:267
@@ -54,6 +54,37 @@ def sc_minn_streaming_metrics_batched(x, symbol_len: int | None = None, *, preci
         _lib.check(rc, "ofs_sc_minn_metric")
     del torch
     return (outs[3], outs[4], outs[5]), (outs[0], outs[1], outs[2])
+
+
+# ---- resumable chunked metrics (csrc/win_chunk.hip, ofs_win_metric_chunk) -------------------
+class SCChunkedMetric(WindowMetricChunked):
+    """``schmidl_cox_streaming_metric`` (R over both halves) for B complex64 streams that arrive in
+    chunks (``ofs_win_metric_chunk`` kind 2); any chunking equals the one-shot batched call bit for bit.
+    See ``WindowMetricChunked``."""
+
+    def __init__(self, B: int, n_branch: int = 1, symbol_len: int | None = None, outputs=("M", "P", "R"),
+                 device=None):
+        super().__init__("comb", B, n_branch, N_FFT if symbol_len is None else symbol_len, outputs, device)
+
+
+class MinnChunkedMetric(WindowMetricChunked):
+    """``minn_streaming_metric`` for B complex64 streams that arrive in chunks (``ofs_win_metric_chunk``
+    kind 3); any chunking equals the one-shot batched call bit for bit.  See ``WindowMetricChunked``."""
+
+    def __init__(self, B: int, n_branch: int = 1, symbol_len: int | None = None, outputs=("M", "P", "R"),
+                 device=None):
+        super().__init__("minn", B, n_branch, N_FFT if symbol_len is None else symbol_len, outputs, device)
+
+
+class SCMinnChunkedMetrics(SCMinnChunked):
+    """Both detector metrics on the same chunks: ``push(x)`` returns ``(minn, sc)`` as
+    ``sc_minn_streaming_metrics_batched`` orders them, from two launches (kinds 3 and 2).  Each equals
+    its own one-shot call (``minn_streaming_metric_batched`` / ``schmidl_cox_streaming_metric_batched``)
+    bit for bit; the fused one-shot kernel rounds its S&C energy differently and is not the yardstick."""
+
+    def __init__(self, B: int, n_branch: int = 1, symbol_len: int | None = None, outputs=("M", "P", "R"),
+                 device=None):
+        super().__init__(B, n_branch, N_FFT if symbol_len is None else symbol_len, outputs, device)
 
 
 # ---- detector back end (combined_sc_min.py:167-259, :337-365), csrc/postproc.hip -------------

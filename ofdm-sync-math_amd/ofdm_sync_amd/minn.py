@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._metrics import window_metric
+from ._metrics import WindowMetricChunked, window_metric
 
 N_FFT = 2048  # core.py:6
 
@@ -24,6 +24,17 @@ def minn_streaming_metric_parameterized(rx, symbol_len: int, *, precision=None):
 def minn_streaming_metric_batched(x, symbol_len: int | None = None, *, precision=None):
     return window_metric("minn", x, N_FFT if symbol_len is None else symbol_len, batched=True,
                          precision=precision)
+
+
+class MinnChunkedMetric(WindowMetricChunked):
+    """``minn_streaming_metric(_parameterized)`` for B complex64 streams that arrive in chunks
+    (``ofs_win_metric_chunk`` kind 3): ``push(x)`` returns M / P / R at the chunk's samples, element i
+    at output index d = d0 + i; any chunking equals the one-shot batched call bit for bit.  The symbol
+    length is the module global ``N_FFT`` at construction unless given.  See ``WindowMetricChunked``."""
+
+    def __init__(self, B: int, n_branch: int = 1, symbol_len: int | None = None, outputs=("M", "P", "R"),
+                 device=None):
+        super().__init__("minn", B, n_branch, N_FFT if symbol_len is None else symbol_len, outputs, device)
 
 
 def _trailing_average(x, win: int):

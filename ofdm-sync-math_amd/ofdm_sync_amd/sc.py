@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._metrics import window_metric
+from ._metrics import WindowMetricChunked, window_metric
 
 N_FFT = 2048            # core.py:6
 CYCLIC_PREFIX = 512     # core.py:8
@@ -22,6 +22,16 @@ def sc_streaming_metric(rx, *, precision=None):
 def sc_streaming_metric_batched(x, N: int | None = None, *, precision=None):
     """Batched S&C metric over x[B, n_branch, T]; device tensors [B, T-N+1]."""
     return window_metric("sc", x, N_FFT if N is None else N, batched=True, precision=precision)
+
+
+class SCChunkedMetric(WindowMetricChunked):
+    """``sc_streaming_metric`` for B complex64 streams that arrive in chunks (``ofs_win_metric_chunk``
+    kind 1): ``push(x)`` returns M / P / R at the chunk's samples, element i at output index
+    d = d0 + i; any chunking equals the one-shot batched call bit for bit.  The symbol length is the
+    module global ``N_FFT`` at construction unless ``N`` is given.  See ``WindowMetricChunked``."""
+
+    def __init__(self, B: int, n_branch: int = 1, N: int | None = None, outputs=("M", "P", "R"), device=None):
+        super().__init__("sc", B, n_branch, N_FFT if N is None else N, outputs, device)
 
 
 def find_plateau_end_from_metric(M, cp_len: int, lookahead: int | None = None, smooth_win: int = 8) -> int:
