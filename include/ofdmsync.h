@@ -492,6 +492,10 @@ int32_t ofs_cp_cfo(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64
  * status [B] int32: 0 searched, 1 empty range (the reference then falls back to
  * estimate_cfo_from_cp at est: the caller runs ofs_cp_cfo; d_out = est, cfo_out = NaN).
  * Windows are summed directly in fp64 (no prefix differences).
+ * Mode 1 skips a window whose |P_w(d)| is NaN (it never compares above, as in the reference's
+ * `mag > best_mag`); a non-empty range without any comparable window gives the reference's
+ * initial values (core.py:289-291): d_out = the range's first offset max(0, est - span),
+ * P_out = (0, 0), cfo_out = -0.0, status 0.
  */
 #define OFS_CPS_ROBUST 0
 #define OFS_CPS_PEAK   1

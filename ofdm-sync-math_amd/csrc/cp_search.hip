@@ -12,6 +12,9 @@
 // The search range is the reference's: d_lo = max(0, est - span),
 // d_hi = min(T - (N + w), est + span); an empty range is reported as status 1 (the reference
 // falls back to estimate_cfo_from_cp at est; the caller does the same with ofs_cp_cfo).
+// A window whose |P| is NaN never compares above (mag > best_mag is false), so it is skipped; a mode 1
+// range in which no window is comparable (every |P(d)| NaN) keeps the reference's initial values
+// (core.py:289-291): d = d_lo, P = (0, 0), cfo = -0.0, status 0.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -112,6 +115,7 @@ __global__ __launch_bounds__(SW) void cp_search_kernel(CpsArgs a) {
                     sv[0][0] = sv[k][0]; sv[0][1] = sv[k][1]; sv[0][2] = sv[k][2]; si[0] = si[k];
                 }
             br_ = sv[0][1]; bi_ = sv[0][2]; bd = si[0];
+            if (bd == INT64_MAX) bd = d_lo;               // no comparable window: best_d = d_lo, best_P = 0 (core.py:289-291)
         }
     }
     if (t == 0) {

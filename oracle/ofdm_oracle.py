@@ -366,6 +366,27 @@ def _cp_window(x, d, n_fft, w):
     return np.sum(x[:, d:d + w] * np.conj(x[:, d + n_fft:d + n_fft + w]))
 
 
+def _cp_sum(x, lo, hi, n_fft, win):
+    """core.py:224-228: sum of P_win(d) over [lo, hi), accumulated from 0j in ascending d."""
+    P = 0j
+    for d in range(lo, hi):
+        P += _cp_window(x, d, n_fft, win)
+    return P
+
+
+def _cp_first_max(x, lo, hi, n_fft, w):
+    """core.py:289-300: (P(d*), d*) of the first d in [lo, hi) with |P(d)| above every earlier one (strict >
+    from -1.0); a window whose |P| is NaN never compares above, so a range without a comparable window
+    keeps (0j, lo)."""
+    best, bmag, bd = 0j, -1.0, lo
+    for d in range(lo, hi):
+        P = _cp_window(x, d, n_fft, w)
+        m = float(np.abs(P))
+        if m > bmag:
+            best, bmag, bd = P, m, d
+    return best, bd
+
+
 def cp_cfo_robust(rx, est, n_fft, cp_len, fs_hz, span=None, win_len=None):
     """core.estimate_cfo_from_cp_robust (core.py:199-231): angle of sum_d P_win(d) over
     d in [max(0, est-span), min(T-(N+win), est+span)); empty range -> estimate_cfo_from_cp at
@@ -377,9 +398,7 @@ def cp_cfo_robust(rx, est, n_fft, cp_len, fs_hz, span=None, win_len=None):
     lo, hi = max(0, est - span), min(T - (n_fft + win), est + span)
     if hi <= lo:
         return cp_cfo(x, est, n_fft, min(cp_len, win), fs_hz)[0]
-    P = 0j
-    for d in range(lo, hi):
-        P += _cp_window(x, d, n_fft, win)
+    P = _cp_sum(x, lo, hi, n_fft, win)
     return float(-np.angle(P) * fs_hz / (2 * np.pi * n_fft))
 
 
@@ -393,13 +412,21 @@ def cp_cfo_peak(rx, est, n_fft, cp_len, fs_hz, span=None):
     lo, hi = max(0, est - span), min(T - (n_fft + cp_len), est + span)
     if hi <= lo:
         return cp_cfo(x, est, n_fft, cp_len, fs_hz)[0], int(est)
-    best, bmag, bd = 0j, -1.0, lo
-    for d in range(lo, hi):
-        P = _cp_window(x, d, n_fft, cp_len)
-        m = float(np.abs(P))
-        if m > bmag:
-            best, bmag, bd = P, m, d
+    best, bd = _cp_first_max(x, lo, hi, n_fft, cp_len)
     return float(-np.angle(best) * fs_hz / (2 * np.pi * n_fft)), int(bd)
+
+
+def cp_search(rx, est, n_fft, win, span, mode, fs_hz):
+    """The batched search contract (ofs_cp_search) on one stream, from the loops of cp_cfo_robust (mode 0)
+    and cp_cfo_peak (mode 1): (status, d, P, cfo).  An empty range is status 1 with d = est and NaN P and
+    cfo (the drop-ins then fall back to cp_cfo at est); mode 0 reports d = est."""
+    x = _as2d(rx)
+    T = x.shape[1]
+    lo, hi = max(0, est - span), min(T - (n_fft + win), est + span)
+    if hi <= lo:
+        return 1, int(est), complex(np.nan, np.nan), float("nan")
+    P, d = (_cp_sum(x, lo, hi, n_fft, win), est) if mode == 0 else _cp_first_max(x, lo, hi, n_fft, win)
+    return 0, int(d), complex(P), float(-np.angle(P) * fs_hz / (2 * np.pi * n_fft))
 
 
 def find_cp_start(rx, est, n_fft, cp_len, search_half=1024):

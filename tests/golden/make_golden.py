@@ -29,6 +29,8 @@ Reference entry points exercised (file:line into /root/reference):
   sc.find_plateau_end_from_metric / minn.find_minn_peak / combined_sc_min.find_minn_peak,
   _streaming_peak_detector and the gate inside run_simulation, on the exact tie and non-finite
   streams of tests/post_streams.py (gen_post_exact)
+  core.py:199-336  the CP searches on the exact tie and non-finite streams of tests/cp_streams.py
+  (gen_cp_search_exact)
 Input builders used only to synthesise realistic streams (not part of the parity surface):
   sync_aa.build_aa_preamble / apply_channel_multi_antenna / apply_cfo / quantize_adc,
   sc.build_sc_preamble, combined_sc_min.build_minn_preamble, minn_rtl.build_minn_preamble_generic,
@@ -653,6 +655,54 @@ def gen_post_exact(R, cases):
             cases[f"post_exact_{op}_n{n}"] = d
 
 
+def gen_cp_search_exact(R, cases):
+    """The reference's own CP searches (core.py:199-336) on exact tie and non-finite streams of
+    tests/cp_streams.py, configuration N = 16, w = 3, two branches: tie and axis-aligned plateaus, all-zero and
+    empty ranges, and all-NaN, partly-NaN and Inf streams with the default span (w // 2) and with span 300.  Kind
+    "cp_search_exact": the unique streams once (x), and per record the stream's row, est and span and what
+    estimate_cfo_from_cp_peak_with_index, estimate_cfo_from_cp_peak, find_cp_start_via_corr (search_half =
+    span) and estimate_cfo_from_cp_robust (cp_len = 2 w, win_len = w) returned."""
+    here = Path(__file__).resolve().parent
+    for p_ in (here.parent, here.parent.parent / "oracle"):
+        if str(p_) not in sys.path:
+            sys.path.insert(0, str(p_))
+    import cp_streams as S
+    core = R["core"]
+    N, w, nb = 16, 3, 2
+    keep = {"ties": {"lane", "wave", "stride", "same_thread", "second_pass_lane", "second_pass_wave", "first_offset"},
+            "axis": {"axis0_0", "axis1_1", "axis2_2", "axis3_3"}, "zsum": {"zeros", "cancel_real"},
+            "empty": {"span0@100", "span0@T"},
+            "nonfinite": {"nan_in_every_window", "nan_stream", "nan_first_window", "nan_zero_bg", "inf", "inf_pair",
+                          "inf_zero_bg"}}
+    far = {"nan_stream", "nan_zero_bg", "inf_zero_bg"}       # of the span 300 launch
+    rows, uniq, rec, names = [], {}, {}, []
+    for c in S.cases():
+        if c.op != "search" or (c.N, c.w, c.nb) != (N, w, nb) or c.mode != S.PEAK or c.T != S.T_MAIN:
+            continue
+        for b, nm in enumerate(c.names):
+            if nm not in keep.get(c.family, ()) or (c.family == "nonfinite" and c.span != w // 2 and nm not in far):
+                continue
+            x, e, sp = np.array(c.x[b]), int(c.est[b]), int(c.span)
+            key = x.tobytes()
+            if key not in uniq:
+                uniq[key] = len(rows)
+                rows.append(x)
+            with np.errstate(all="ignore"):
+                cfo, d = core.estimate_cfo_from_cp_peak_with_index(x, e, N, w, S.FS, span=sp)
+                out = dict(row=uniq[key], est=e, span=sp, peak_cfo=cfo, peak_d=d,
+                           peak_only=core.estimate_cfo_from_cp_peak(x, e, N, w, S.FS, span=sp),
+                           find_start=core.find_cp_start_via_corr(x, e, N, w, search_half=sp),
+                           robust=core.estimate_cfo_from_cp_robust(x, e, N, 2 * w, S.FS, span=sp, win_len=w))
+            names.append(f"{c.family}:{nm}:s{sp}")
+            for k, v in out.items():
+                rec.setdefault(k, []).append(v)
+    xs = np.array(rows).astype(np.complex64)                 # small integers, NaN and Inf: complex64 holds them
+    assert np.array_equal(xs.astype(complex), np.array(rows), equal_nan=True)
+    cases["cp_search_exact"] = dict(kind="cp_search_exact", x=xs, names=np.array(names),
+                                    n_fft=np.int64(N), win=np.int64(w), fs=np.float64(S.FS),
+                                    **{k: np.array(v) for k, v in rec.items()})
+
+
 def gen_synth(R, cases):
     """Input builders the GPU synthesis restates (synth.py / synth.hip): the measured CIR banks
     (channel.load_measured_cir, channel.py:15-48), the [A][A] preambles (sync_aa.build_aa_preamble,
@@ -696,6 +746,7 @@ def main():
     gen_zc(R, cases)
     gen_post(R, cases)
     gen_post_exact(R, cases)
+    gen_cp_search_exact(R, cases)
     gen_synth(R, cases)
     OUT.mkdir(parents=True, exist_ok=True)
     only = set(sys.argv[1:])               # optional case names: rewrite only those files

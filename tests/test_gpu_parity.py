@@ -392,14 +392,17 @@ def test_cp_search_batched_vs_oracle(fmt):
         xd = torch.from_numpy(x.astype(np.complex64 if fmt == "c64" else np.complex128)).cuda()
     xr = x.astype(np.complex64).astype(np.complex128) if fmt == "c64" else x
     for mode, win, span in ((core.CPS_ROBUST, 64, 40), (core.CPS_PEAK, cp, 200)):
-        cfo, d, _, st = core.cp_search_batched(xd, est, N, win, span, mode, 1e6)
-        cfo, d, st = cfo.cpu().numpy(), d.cpu().numpy(), st.cpu().numpy()
+        cfo, d, P, st = core.cp_search_batched(xd, est, N, win, span, mode, 1e6)
+        cfo, d, P, st = cfo.cpu().numpy(), d.cpu().numpy(), P.cpu().numpy(), st.cpu().numpy()
         for b in range(B):
             lo, hi = max(0, est[b] - span), min(T - (N + win), est[b] + span)
             assert st[b] == (1 if hi <= lo else 0)
             if st[b]:
                 assert d[b] == est[b]
                 continue
+            # integer samples: every partial sum is an integer below 2^53, so P (sum_d P(d) in robust
+            # mode, P(d*) in peak mode) is exact in any order and equals the oracle's bit for bit
+            assert P[b] == O.cp_search(xr[b], int(est[b]), N, win, span, mode, 1e6)[2]
             if mode == core.CPS_ROBUST:
                 ref = O.cp_cfo_robust(xr[b], int(est[b]), N, 2 * win, 1e6, span=span, win_len=win)
                 assert abs(cfo[b] - ref) < 1e-6

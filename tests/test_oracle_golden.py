@@ -21,7 +21,7 @@ def test_fixture_inventory():
     names = {os.path.basename(p)[:-4] for p in CASES}
     assert {"aa_clean_L512", "aa_cfo_L512", "aa_int12_L128", "sc_N64_cfg1",
             "comb_sc_N2048_cir1_2br", "comb_minn_N2048_cir1_2br", "rtl_Q64_int12",
-            "rtl_Q512_int12", "cp_cfo"} <= names
+            "rtl_Q512_int12", "cp_cfo", "cp_search_exact"} <= names
 
 
 @pytest.mark.parametrize("path", CASES, ids=lambda p: os.path.basename(p)[:-4])
@@ -120,6 +120,34 @@ def test_oracle_matches_reference_golden(path):
         assert close([p[0] for p in pk], d["peak_1br_s300_cfo"]) and [p[1] for p in pk] == list(d["peak_1br_s300_d"])
         assert [O.find_cp_start(x, e, N, cp) for e in est] == list(d["find_start"])
         assert [O.find_cp_start(x, e, N, cp, search_half=64) for e in est] == list(d["find_start_h64"])
+    elif kind == "cp_search_exact":
+        # the reference's own searches on exact tie and non-finite streams of tests/cp_streams.py: indices
+        # equal; cfo NaN where the reference's is, of the same sign where it is zero, else within 1e-8 Hz
+        N, w, fs = int(d["n_fft"]), int(d["win"]), float(d["fs"])
+        names = [str(n) for n in d["names"]]
+        assert len(names) >= 25 and {n.split(":")[0] for n in names} == {"ties", "axis", "zsum", "empty", "nonfinite"}
+
+        def cfo_ok(got, ref):
+            if np.isnan(ref) or np.isnan(got):
+                return bool(np.isnan(ref) and np.isnan(got))
+            return abs(got - ref) <= 1e-8 and (ref != 0 or (got == 0 and np.signbit(got) == np.signbit(ref)))
+
+        all_nan = 0
+        with np.errstate(all="ignore"):
+            for k, name in enumerate(names):
+                x, e, sp = d["x"][int(d["row"][k])], int(d["est"][k]), int(d["span"][k])
+                cfo, dd = O.cp_cfo_peak(x, e, N, w, fs, span=sp)
+                assert dd == int(d["peak_d"][k]) and cfo_ok(cfo, d["peak_cfo"][k]) and cfo_ok(cfo, d["peak_only"][k]), name
+                assert O.find_cp_start(x, e, N, w, sp) == int(d["find_start"][k]), name
+                assert cfo_ok(O.cp_cfo_robust(x, e, N, 2 * w, fs, span=sp, win_len=w), d["robust"][k]), name
+                st, sd, sP, scfo = O.cp_search(x, e, N, w, sp, 1, fs)
+                lo, hi = max(0, e - sp), min(x.shape[1] - (N + w), e + sp)
+                assert st == (hi <= lo) and sd == dd and (st == 1 or cfo_ok(scfo, d["peak_cfo"][k])), name
+                if st == 0 and name.startswith("nonfinite:nan_") and sP == 0:
+                    # a range without a comparable window: the reference keeps best_d = d_lo and best_P = 0
+                    assert dd == lo and cfo == 0 and np.signbit(cfo), name
+                    all_nan += 1
+        assert all_nan >= 3
     elif kind == "park":
         ds, M, P, E = O.park_metric(d["x"], int(d["N"]))
         assert np.array_equal(ds, d["ds"])
