@@ -579,6 +579,76 @@ int32_t ofs_park_metric(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, 
                         int32_t N, int32_t precision, void* M, void* P, void* E, void* stream);
 
 /*
+ * Resumable chunked Park metric with a running peak, for streams of any length: the chunk-fed form of
+ * ofs_park_metric.  The reference's park.park_streaming_metric (park.py:64-114) and its detection
+ * argmax(M) (park.py:161-164) are the specification.
+ *
+ * A stream is fed in consecutive chunks of Tc samples; ofs_park_metric_chunk returns M, P, E at the
+ * chunk's samples and keeps what the next call needs (the last 2*half + 16 samples at most, in the
+ * input's own format, and the running peak of M) in a caller-owned state buffer on the device.  The
+ * library allocates nothing, reads no environment and keeps no global state.
+ *   in_fmt, precision   one of the pairs (OFS_C64, OFS_FP32), (OFS_C128, OFS_FP64), (OFS_CI16, OFS_FP64).
+ *   x       [B][n_br][Tc] samples in in_fmt (this call's chunk), branches summed; n_br >= 1.
+ *   N       symbol length, half = N / 2 >= 1, N <= 8190 (fp32) / 4094 (fp64) as for ofs_park_metric.
+ *   state   [B][ofs_park_chunk_state_bytes(in_fmt, n_br, N)] bytes, 16-byte aligned, device memory.
+ *           The layout is opaque; ALL-ZERO BYTES ARE A FRESH STREAM, so any subset of streams is reset
+ *           with a memset of its rows (stream-ordered with the calls).  One state row belongs to one
+ *           stream: in_fmt, n_br and N must not change between the calls of a stream, and the calls of
+ *           a stream must be ordered (same HIP stream, or synchronised by the caller).
+ *   M, P, E [B][Tc] f32 / c64 / f32 (fp32) or f64 / c128 / f64 (fp64), EACH nullable.  Element j of a
+ *           call belongs to the stream's newest sample n = (samples of earlier calls) + j, that is to
+ *           the reference's centre index d = n - half + 1, the first d whose window
+ *           x[d-half+1 .. d+half-1] is complete.  Elements with d < half (the reference has no such
+ *           output) are written as +0.0 (all-zero bits) for any input, NaN and Inf included.  The fill
+ *           phase is decided per stream on n, so after a reset of some state rows the streams of one
+ *           call may be at different n.
+ *   d0      [B] int64, nullable; every call writes the d of its element 0.
+ *   peak_index [B] int64, peak_value [B] f64, each nullable: after every call the running np.argmax of
+ *           M over the outputs the reference has on the stream's n samples so far (half <= d <=
+ *           n - half - 1, see below), as ofs_row_argmax defines it (the first maximal element; the
+ *           first NaN once one has appeared): the peak's d and its M widened to f64; -1 and 0.0 while
+ *           the stream has no such output (n < 2*half + 1).  The peak advances only in calls that pass
+ *           M.
+ *   final   != 0 changes nothing in the outputs of this call (the peak outputs include its M); the
+ *           state is a fresh stream again after the call.
+ *   Tc      1 .. ofs_park_chunk_max_samples(in_fmt, n_br, N) = 2^30; Tc = 0 with final != 0 is a flush:
+ *           no samples, d0 and the peak outputs written, the streams fresh afterwards (x and the arrays
+ *           unused).
+ * EQUIVALENCE GUARANTEE.  For any split of a stream of T >= 2*half + 1 samples into chunks, each output
+ * array concatenated over the calls, with its first 2*half - 1 elements dropped, begins with, BIT FOR
+ * BIT, the [T - 2*half] array that ONE ofs_park_metric call with the same in_fmt and precision returns
+ * on the whole stream - whichever of M / P / E are requested here.  One element follows it: the output
+ * d = T - half, whose window ends at the stream's last sample.  The reference and ofs_park_metric stop
+ * one output earlier (they ask for sample d + half, which no sum reads); that element is what
+ * ofs_park_metric returns at d on any longer stream.  The peak follows the reference: an output joins
+ * it in the call that brings sample d + half, so after the last call peak_index - half and peak_value
+ * equal what ofs_row_argmax returns on the one-shot call's M, and after every call they are the
+ * argmax of what the one-shot call returns on the samples so far.  Variant PARK_DIRECT
+ * (ofs_debug_set_variant) selects the energy form of both calls alike, so the pair stays equal.
+ * Exception: behind non-finite samples an output word is a NaN exactly where the one-shot call's is,
+ * but its SIGN bit is outside the guarantee (as for ofs_win_metric_chunk).
+ * STREAM LENGTH.  The state carries samples and the peak, no sums: every output is computed from its
+ * own window alone, so nothing degrades with the stream's length.  Only the sample count n limits it,
+ * and that is an int64.
+ * Calls are stream-ordered and never synchronise with the host: consecutive chunks may be enqueued back
+ * to back (two kernels per call: the metric, then one small workgroup per stream that writes the
+ * history, folds the peak and advances the state).  OFS_EINVAL (before any launch): a (in_fmt,
+ * precision) pair other than the three above, n_br < 1, half < 1 or N above the limit, Tc < 0 or above
+ * the limit, Tc = 0 without final, B < 0, a null or misaligned state with B > 0, a null x with
+ * B * Tc > 0, peak_index or peak_value with a null M and B * Tc > 0.  B = 0 is a valid no-op.
+ * ofs_park_chunk_state_bytes returns the bytes of ONE stream's state (a multiple of 16) and
+ * ofs_park_chunk_max_samples the largest Tc of one call; both return OFS_EINVAL (< 0) for an
+ * unsupported shape.
+ */
+int64_t ofs_park_chunk_state_bytes(int32_t in_fmt, int32_t n_br, int32_t N);
+int64_t ofs_park_chunk_max_samples(int32_t in_fmt, int32_t n_br, int32_t N);
+int32_t ofs_park_metric_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t Tc,
+                              int32_t N, int32_t precision, void* state,
+                              void* M, void* P, void* E, int64_t* d0,
+                              int64_t* peak_index, double* peak_value,
+                              int32_t final, void* stream);
+
+/*
  * ZC matched filter / normaliser (fp64): replaces zc_v2.matched_filter_correlation
  * (zc_v2.py:244-254), normalize_correlation (:257-271), the branch combine of
  * detect_zc_preamble (:489-503) and the inline combiner of zc.py:106-126.

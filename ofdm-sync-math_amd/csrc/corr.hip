@@ -25,147 +25,29 @@
 #include <algorithm>
 #include "ofdmsync.h"
 #include "ofs_common.h"
+#include "park_tile.h"
 
 namespace {
 
-template <class R> struct C2;
-template <> struct C2<float> { using T = float2; };
-template <> struct C2<double> { using T = double2; };
+using namespace ofs_tile;          // park_tile.h: C2, ld_c, CW / OPT / CD / PADF, split_stride, park_tile
 
-template <int FMT, class R>
-__device__ __forceinline__ typename C2<R>::T ld_c(const void* p, int64_t i) {
-    typename C2<R>::T o;
-    if constexpr (FMT == OFS_C64) {
-        const float2 v = reinterpret_cast<const float2*>(p)[i];
-        o.x = (R)v.x; o.y = (R)v.y;
-    } else if constexpr (FMT == OFS_C128) {
-        const double2 v = reinterpret_cast<const double2*>(p)[i];
-        o.x = (R)v.x; o.y = (R)v.y;
-    } else {
-        const short2 v = reinterpret_cast<const short2*>(p)[i];
-        o.x = (R)v.x; o.y = (R)v.y;
-    }
-    return o;
-}
-
-constexpr int CW = 256;          // threads per workgroup (Park, matched filter)
-constexpr int OPT = 8;           // consecutive outputs per thread
-constexpr int CD = CW * OPT;     // outputs per workgroup tile
-constexpr int PADF = OPT;        // front pad of the staged tile (Park's backward window)
-
-__host__ __device__ constexpr int64_t split_stride(int64_t len) { return (len + OPT - 1) / OPT | 1; }
-
-// ------------------------------------------------------------------------------------------
-// Park: P(d) = Σ_br Σ_{k<half} x[d-k]·x[d+k]; E(d) = Σ_br Σ_{k<half} |x[d+k]|²;
-//       M = |P|²/max(E,1e-12)²;  d = half + i, i in [0, nout)   (park.py:76-113)
-// Tile: global g in [g0, g0 + len), g0 = d0 - half + 1 - PADF, zero outside [0, T).
-// Thread t, output q: backward b_q = x[d-k], forward f_q = x[d+k]; per step k one new
-// backward value (q = 0) and one new forward value (q = OPT-1) come from LDS; the others
-// rotate through a ring whose slot is (q ∓ k) mod OPT, resolved at compile time by
-// unrolling k by OPT.
-// ------------------------------------------------------------------------------------------
-// Energy: the OPT outputs of a thread share all but the first / last few samples of their
-// windows, so (SPLIT, half >= OPT) E_q = C + H_q + T_q with C = Σ_{k=OPT-1}^{half-1} |x[d0+k]|²
-// (accumulated once, from output 0's forward values), H_q = Σ_{k=q}^{OPT-2} |x[d0+k]|² and
-// T_q = Σ_{k=half}^{half+q-1} |x[d0+k]|² — sums of non-negative terms only, 2 instead of 2·OPT FMAs
-// per step.
-// (packed forms of the complex MAC measured no faster for fp32 - vector-type swizzles 3.95 ms, two
-// inline-asm v_pk_fma_f32 with op_sel 2.67 ms, against 2.51 ms for the scalar FMAs: r02ab)
-template <class R, class V>
-__device__ __forceinline__ void park_mac(const V& b, const V& f, R& pr, R& pi) {
-    pr = fma(b.x, f.x, fma(-b.y, f.y, pr));
-    pi = fma(b.x, f.y, fma(b.y, f.x, pi));
-}
-
+// Park (ofs_park_metric): tile blockIdx.x of stream blockIdx.y, outputs i in [0, nout); the tile body
+// is park_tile() of park_tile.h, shared with the chunked kernel of park_chunk.hip.
 template <int FMT, class R, bool SPLIT>
 __global__ __launch_bounds__(CW) void park_kernel(const void* x, int64_t T, int nb, int half,
                                                   int64_t nout, R* __restrict__ Mo,
                                                   R* __restrict__ Po, R* __restrict__ Eo) {
     using V = typename C2<R>::T;
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    V* seg = reinterpret_cast<V*>(smem_raw);
-    const int t = threadIdx.x;
     const int64_t b = blockIdx.y;
-    const int64_t i0 = (int64_t)blockIdx.x * CD;
-    const int64_t d0 = half + i0;
-    const int64_t g0 = d0 - half + 1 - PADF;
-    const int64_t len = CD + 2 * (int64_t)half - 2 + 2 * PADF;
-    const int64_t S = split_stride(len);
-    const int ksteps = (half + OPT - 1) / OPT * OPT;
-
-    R pr[OPT], pi[OPT], en[OPT];
-#pragma unroll
-    for (int q = 0; q < OPT; ++q) { pr[q] = 0; pi[q] = 0; en[q] = 0; }
-
-    for (int br = 0; br < nb; ++br) {
-        const int64_t base = (b * nb + br) * T;
-        __syncthreads();
-        for (int64_t j = t; j < len; j += CW) {
-            const int64_t g = g0 + j;
-            V v; v.x = 0; v.y = 0;
-            if (g >= 0 && g < T) v = ld_c<FMT, R>(x, base + g);
-            seg[(j % OPT) * S + j / OPT] = v;
-        }
-        __syncthreads();
-        // seg index of x[d0 + OPT*t + q + m] is PADF + half - 1 + OPT*t + q + m
-        auto at = [&](int64_t j) -> V { return seg[(j % OPT) * S + j / OPT]; };
-        const int64_t c0 = PADF + half - 1 + (int64_t)OPT * t;
-        V bw[OPT], fw[OPT];
-#pragma unroll
-        for (int q = 0; q < OPT; ++q) { bw[q] = at(c0 + q); fw[q] = at(c0 + q); }
-        R ce = 0;                                         // SPLIT: C of this branch
-        for (int kk = 0; kk < ksteps; kk += OPT) {
-#pragma unroll
-            for (int u = 0; u < OPT; ++u) {
-                const int k = kk + u;
-                if (k < half) {
-#pragma unroll
-                    for (int q = 0; q < OPT; ++q) {
-                        const V bq = bw[(q - u + OPT) % OPT];
-                        const V fq = fw[(q + u) % OPT];
-                        park_mac<R, V>(bq, fq, pr[q], pi[q]);
-                        if (!SPLIT) en[q] = fma(fq.x, fq.x, fma(fq.y, fq.y, en[q]));
-                    }
-                    if (SPLIT && (kk > 0 || u >= OPT - 1)) {
-                        const V f0 = fw[u % OPT];         // x[d0 + k]
-                        ce = fma(f0.x, f0.x, fma(f0.y, f0.y, ce));
-                    }
-                }
-                // next step: new backward x[d0+OPT t-(k+1)] into slot of b_{OPT-1},
-                //            new forward  x[d0+OPT t+OPT-1+k+1] into slot of f_0
-                bw[(OPT - 1 - u + OPT) % OPT] = at(c0 - (k + 1));
-                fw[u % OPT] = at(c0 + OPT + k);
-            }
-        }
-        if constexpr (SPLIT) {
-            R hd[OPT], tl[OPT];                           // |x[d0+k]|², |x[d0+half+k]|², k < OPT-1
-#pragma unroll
-            for (int k = 0; k < OPT - 1; ++k) {
-                const V h = at(c0 + k), w = at(c0 + half + k);
-                hd[k] = fma(h.x, h.x, h.y * h.y);
-                tl[k] = fma(w.x, w.x, w.y * w.y);
-            }
-            R hs = 0, ts = 0;
-#pragma unroll
-            for (int q = OPT - 1; q >= 0; --q) {          // H_q: suffix of hd from q
-                en[q] += ce + hs;
-                if (q > 0) hs += hd[q - 1];
-            }
-#pragma unroll
-            for (int q = 1; q < OPT; ++q) { ts += tl[q - 1]; en[q] += ts; }   // T_q
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < OPT; ++q) {
-        const int64_t i = i0 + (int64_t)OPT * t + q;
-        if (i < nout) {
-            const int64_t o = b * nout + i;
-            const R e = en[q] > (R)1e-12 ? en[q] : (R)1e-12;
-            if (Mo) Mo[o] = (pr[q] * pr[q] + pi[q] * pi[q]) / (e * e);
-            if (Po) { Po[2 * o] = pr[q]; Po[2 * o + 1] = pi[q]; }
-            if (Eo) Eo[o] = en[q];
-        }
-    }
+    auto load = [&](int br, int64_t g) -> V {            // sample g of branch br, zero outside [0, T)
+        V v; v.x = 0; v.y = 0;
+        if (g >= 0 && g < T) v = ld_c<FMT, R>(x, (b * nb + br) * T + g);
+        return v;
+    };
+    park_tile<R, SPLIT>(reinterpret_cast<V*>(smem_raw), (int64_t)blockIdx.x * CD, nb, half, load, 0, nout, 0,
+                        Mo ? Mo + b * nout : nullptr, Po ? Po + 2 * b * nout : nullptr,
+                        Eo ? Eo + b * nout : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -955,8 +837,7 @@ static int set_lds(K k, size_t bytes) {
 template <int FMT, class R>
 static int park_launch(const void* x, int64_t B, int nb, int64_t T, int half, int64_t nout,
                        void* M, void* P, void* E, hipStream_t st) {
-    const int64_t len = CD + 2 * (int64_t)half - 2 + 2 * PADF;
-    const size_t lds = (size_t)split_stride(len) * OPT * sizeof(typename C2<R>::T);
+    const size_t lds = park_tile_lds<R>(half);
     // shared-window energy needs half >= OPT - 1 (variant PARK_DIRECT=1: per-output energy sums, A/B)
     const bool direct = ofs::variant_on(ofs::V_PARK_DIRECT);
     auto k = (half >= OPT - 1 && !direct) ? park_kernel<FMT, R, true> : park_kernel<FMT, R, false>;

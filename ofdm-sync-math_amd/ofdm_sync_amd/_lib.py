@@ -113,6 +113,10 @@ def _declare(lib):
                                        ctypes.c_uint64, c_int32, P, P, P, P]),
         "ofs_park_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, P, P,
                                       P, P]),
+        "ofs_park_chunk_state_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+        "ofs_park_chunk_max_samples": (c_int64, [c_int32, c_int32, c_int32]),
+        "ofs_park_metric_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, P, P, P, P,
+                                            P, P, P, c_int32, P]),
         "ofs_zc_correlate": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, P, c_int32, c_double,
                                        c_int32, P, P, P, P]),
         "ofs_zc_freq_metric": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,

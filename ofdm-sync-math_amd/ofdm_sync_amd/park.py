@@ -46,3 +46,145 @@ def park_streaming_metric_batched(x, N: int | None = None, *, precision=None):
     batch = _lib.as_batch(x, batched=True)
     prec = _lib.resolve_precision(batch, precision)
     return _run(batch, int(N_FFT if N is None else N), prec)
+
+
+# ---- resumable chunked form (csrc/park_chunk.hip, ofs_park_metric_chunk) -----------------------
+# sample dtype -> (format, precision, real output dtype, complex output dtype)
+_CHUNK_FORMATS = {
+    torch.complex64: (_lib.C64, _lib.FP32, torch.float32, torch.complex64),
+    torch.complex128: (_lib.C128, _lib.FP64, torch.float64, torch.complex128),
+    torch.int16: (_lib.CI16, _lib.FP64, torch.float64, torch.complex128),
+}
+
+
+class ParkChunkResult:
+    """Outputs of one ``ParkChunkedMetric.push``: ``M`` real, ``P`` complex, ``E`` real (float32 /
+    complex64 for complex64 streams, float64 / complex128 otherwise), each ``[B, Tc]`` or None when not
+    requested; ``d0`` ``[B]`` int64, the reference's centre index d of element 0 (element j belongs to
+    d0 + j; elements with d < N // 2 are +0.0); ``peak_index`` ``[B]`` int64 and ``peak_value`` ``[B]``
+    float64, the running argmax of M over the reference's outputs on the samples so far (its d and its
+    M; -1 and 0.0 while there is none), or None without ``track_peak``."""
+    __slots__ = ("M", "P", "E", "d0", "peak_index", "peak_value")
+
+    def __init__(self, M, P, E, d0, peak_index, peak_value):
+        self.M, self.P, self.E, self.d0 = M, P, E, d0
+        self.peak_index, self.peak_value = peak_index, peak_value
+
+
+class ParkChunkedMetric:
+    """Resumable Park timing metric with a running peak over B streams that arrive in chunks
+    (``ofs_park_metric_chunk``).
+
+    The chunk-fed form of ``park_streaming_metric_batched``.  ``dtype`` fixes the sample format and the
+    precision: ``torch.complex64`` (fp32), ``torch.complex128`` (fp64) or ``torch.int16`` (I/Q pairs in a
+    trailing axis of 2, fp64).  ``push(x)`` takes the next ``Tc`` samples of every stream -
+    ``[B, n_branch, Tc]`` (int16: ``[B, n_branch, Tc, 2]``), or without the branch axis for one branch -
+    and returns M / P / E ``[B, Tc]`` at those samples: element j belongs to the stream's newest sample
+    n = samples_seen + j, that is to the reference's centre index d = n - N // 2 + 1; ``d0`` holds the d
+    of element 0 and elements with d < N // 2 are +0.0.  With ``track_peak`` every result also carries
+    the running ``argmax(M)`` of each stream (the reference's detection, park.py:161-164), found on the
+    device as the chunks pass; this needs M, so an M buffer is kept even when ``"M"`` is not in
+    ``outputs`` (``M`` of the result is then None).  Interface and buffer ownership are those of
+    ``_metrics.WindowMetricChunked``: ``push(x, final=True)`` or ``flush()`` leaves fresh streams, the
+    result buffers are this object's (cached per ``Tc``, overwritten in stream order by a later ``push``
+    of that length), ``push`` never synchronises.
+
+    For any chunking of a stream of T >= 2 * (N // 2) + 1 samples, the concatenated outputs with their
+    first 2 * (N // 2) - 1 elements dropped begin with, bit for bit, the one-shot batched call on the
+    whole stream; one more element follows, d = T - N // 2, whose window ends at the last sample (the
+    reference stops one output earlier: it asks for sample d + N // 2).  The peak follows the reference:
+    an output joins it with the push that brings sample d + N // 2, so the last peak is
+    ``ofs_row_argmax`` of the one-shot M.  Nothing is summed across calls, so the
+    stream may be of any length.  ``N=None`` reads the module global ``N_FFT`` at construction; N,
+    n_branch and dtype are fixed for the object's life.  N is at most 8190 (complex64) or 4094.
+    """
+
+    def __init__(self, B: int, n_branch: int = 1, N: int | None = None, dtype=torch.complex64,
+                 outputs=("M", "P", "E"), track_peak: bool = True, device=None):
+        if dtype not in _CHUNK_FORMATS:
+            raise ValueError(f"dtype must be torch.complex64, torch.complex128 or torch.int16, got {dtype!r}")
+        bad = [o for o in outputs if o not in ("M", "P", "E")]
+        if bad:
+            raise ValueError(f"outputs may name 'M', 'P' and 'E', got {bad}")
+        N = int(N_FFT if N is None else N)
+        dev = torch.device(device) if device is not None else _lib.require_gpu()
+        lib = _lib.lib()
+        self.fmt, self.precision, self._rdt, self._cdt = _CHUNK_FORMATS[dtype]
+        nbytes = int(lib.ofs_park_chunk_state_bytes(self.fmt, int(n_branch), N))
+        if nbytes < 0 or B < 0:
+            raise ValueError(f"ParkChunkedMetric needs n_branch >= 1 and 2 <= N <= 8190 (complex64) or 4094 "
+                             f"(complex128, int16) (got n_branch={n_branch}, N={N}, dtype={dtype}, B={B})")
+        self.B, self.n_branch, self.N, self.dtype, self.device = int(B), int(n_branch), N, dtype, dev
+        self.max_chunk = int(lib.ofs_park_chunk_max_samples(self.fmt, self.n_branch, N))
+        self.outputs, self.track_peak = tuple(outputs), bool(track_peak)
+        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
+        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
+        self._fn = lib.ofs_park_metric_chunk
+        self._bufs: dict[int, tuple] = {}
+
+    def _buffers(self, Tc: int):
+        r = self._bufs.get(Tc)
+        if r is None:
+            B, dev, want = self.B, self.device, self.outputs
+            M = torch.empty((B, Tc), dtype=self._rdt, device=dev) if "M" in want and Tc else None
+            P = torch.empty((B, Tc), dtype=self._cdt, device=dev) if "P" in want and Tc else None
+            E = torch.empty((B, Tc), dtype=self._rdt, device=dev) if "E" in want and Tc else None
+            pi = torch.zeros((B,), dtype=torch.int64, device=dev) if self.track_peak else None
+            pv = torch.zeros((B,), dtype=torch.float64, device=dev) if self.track_peak else None
+            res = ParkChunkResult(M, P, E, torch.zeros((B,), dtype=torch.int64, device=dev), pi, pv)
+            # the peak is folded from M: a private M buffer when the caller did not ask for M
+            Mk = torch.empty((B, Tc), dtype=self._rdt, device=dev) if self.track_peak and M is None and Tc else M
+            r = self._bufs[Tc] = (res, Mk)
+        return r
+
+    def _call(self, x, Tc: int, final: bool) -> ParkChunkResult:
+        r, Mk = self._buffers(Tc)
+        rc = self._fn(self.fmt, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.N,
+                      self.precision, self.state.data_ptr(), _lib.ptr(Mk), _lib.ptr(r.P), _lib.ptr(r.E),
+                      r.d0.data_ptr(), _lib.ptr(r.peak_index), _lib.ptr(r.peak_value), int(bool(final)),
+                      _lib.stream_ptr())
+        _lib.check(rc, "ofs_park_metric_chunk")
+        self.samples_seen = 0 if final else self.samples_seen + Tc
+        return r
+
+    def _chunk(self, x, final: bool):
+        """Validate one chunk (before any library call): the contiguous device tensor and its Tc."""
+        iq = (2,) if self.dtype == torch.int16 else ()
+        tail = ", 2" if iq else ""
+        what = (f"[{self.B}, {self.n_branch}, Tc{tail}] {self.dtype}" +
+                (f" (or [{self.B}, Tc{tail}])" if self.n_branch == 1 else ""))
+        if not isinstance(x, torch.Tensor) or x.dtype != self.dtype:
+            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
+        if x.dim() == 2 + len(iq) and self.n_branch == 1:
+            x = x[:, None]
+        if (x.dim() != 3 + len(iq) or x.shape[0] != self.B or x.shape[1] != self.n_branch or
+                tuple(x.shape[3:]) != iq):
+            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
+        Tc = int(x.shape[2])
+        if Tc > self.max_chunk:
+            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
+        if Tc == 0 and not final:
+            raise ValueError("an empty chunk is only valid with final=True (or flush())")
+        if x.device != self.device:
+            x = x.to(self.device)
+        return x.contiguous(), Tc
+
+    def push(self, x: torch.Tensor, final: bool = False) -> ParkChunkResult:
+        """The next chunk of every stream; ``final=True`` also ends the streams (fresh afterwards)."""
+        x, Tc = self._chunk(x, final)
+        return self._call(x, Tc, final)
+
+    def flush(self) -> ParkChunkResult:
+        """End the streams without new samples (M, P, E are None; d0 and the peak are written); the
+        streams are fresh afterwards."""
+        return self._call(None, 0, True)
+
+    def reset(self, mask: torch.Tensor | None = None) -> None:
+        """Make all streams fresh, or those where ``mask`` [B] (bool) is set (stream-ordered, no
+        synchronisation).  ``samples_seen`` restarts only on a full reset."""
+        if mask is None:
+            self.state.zero_()
+            self.samples_seen = 0
+        else:
+            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
+            self.state.masked_fill_(m[:, None], 0)
