@@ -705,6 +705,82 @@ int32_t ofs_zc_freq_metric(int32_t in_fmt, const void* x, int64_t B, int32_t n_b
  * initialised sliding DFT (fp64), 5 the same with the metric rounded to fp32, 6 the one-chunk-per-
  * wave sliding DFT with the metric rounded to fp32, 0 none */
 int32_t ofs_zc_freq_plan(int32_t in_fmt, int32_t precision, int64_t T, int32_t N, int32_t cp);
+
+/*
+ * Resumable chunked zc_freq metric with a running peak, for streams of any length: the chunk-fed form
+ * of ofs_zc_freq_metric on its sliding kernels (plans 4 / 5).  The reference's
+ * zc_freq.compute_frequency_metric (zc_freq.py:62-99) and its detection int(np.argmax(metric))
+ * (zc_freq.py:144) are the specification.
+ *
+ * A stream is fed in consecutive chunks of Tc samples; ofs_zc_freq_metric_chunk returns the metric at
+ * the chunk's samples and keeps what the next call needs (the last N + C samples, in the input's own
+ * format, and the running peak of the metric; C = 64, 128 or 256 is the sliding kernel's chunk length,
+ * a function of N) in a caller-owned state buffer on the device.  The library allocates nothing, reads
+ * no environment and keeps no global state.
+ *   in_fmt, precision   one of the pairs (OFS_C64, OFS_FP32: fp64 arithmetic, the metric rounded to f32),
+ *           (OFS_C128, OFS_FP64), (OFS_CI16, OFS_FP64).
+ *   x       [B][n_br][Tc] samples in in_fmt (this call's chunk); n_br is 1 or 2.
+ *   N, cp   the shapes the sliding kernel takes: N >= 64 and a multiple of 64, the blocks of a window
+ *           within LDS; cp >= 0.
+ *   n_bins, bin_indices, template_bins, template_energy   the template as for ofs_zc_freq_metric (HOST
+ *           pointers, 1 <= n_bins <= 64), passed to every call; it must not change within a stream.  A
+ *           template of mirror pairs (k, N - k) runs the pair body and any other the per-bin body, by
+ *           the one-shot call's own rule.
+ *   state   [B][ofs_zc_freq_chunk_state_bytes(in_fmt, n_br, N, cp)] bytes, 16-byte aligned, device
+ *           memory.  The layout is opaque; ALL-ZERO BYTES ARE A FRESH STREAM, so any subset of streams
+ *           is reset with a memset of its rows (stream-ordered with the calls).  One state row belongs
+ *           to one stream: in_fmt, n_br, N, cp and the template must not change between the calls of a
+ *           stream, and the calls of a stream must be ordered (same HIP stream, or synchronised by the
+ *           caller).
+ *   metric  [B][Tc] f32 (OFS_FP32) or f64, nullable.  Element j of a call belongs to the stream's newest
+ *           sample n = (samples of earlier calls) + j, that is to offset s = n - (N + cp) + 1, the first
+ *           offset whose window x[cp+s .. cp+s+N-1] is complete.  Elements with s < 0 are written as
+ *           +0.0 (all-zero bits) for any input, NaN and Inf included.  The fill phase is decided per
+ *           stream on n, so after a reset of some state rows the streams of one call may be at
+ *           different n.  Without metric the call only takes the samples in.
+ *   off0    [B] int64, nullable; every call writes the s of its element 0.
+ *   peak_index [B] int64, peak_value [B] f64, each nullable: after every call the running np.argmax of
+ *           the metric over the offsets 0 .. s_newest, as ofs_row_argmax defines it (the first maximal
+ *           element; the first NaN once one has appeared): the peak's offset and its metric widened to
+ *           f64; -1 and 0.0 while the stream has no output (n < N + cp).  The peak advances only in
+ *           calls that pass metric.  Every computed output is one the reference has on the samples so
+ *           far, so no output waits for a later call.
+ *   final   != 0 changes nothing in the outputs of this call; the state is a fresh stream again after
+ *           the call.
+ *   Tc      1 .. ofs_zc_freq_chunk_max_samples(in_fmt, n_br, N, cp) = 2^30; Tc = 0 with final != 0 is a
+ *           flush: no samples, off0 and the peak outputs written, the streams fresh afterwards (x and
+ *           metric unused).
+ * EQUIVALENCE GUARANTEE.  For any split of a stream of T >= N + cp samples into chunks, the metric
+ * concatenated over the calls, with its first N + cp - 1 elements dropped, equals BIT FOR BIT the
+ * [T - (N+cp) + 1] array that ONE ofs_zc_freq_metric call with the same in_fmt and precision returns
+ * on the whole stream from its sliding kernel (ofs_zc_freq_plan 4 / 5).  After the last call the peak
+ * equals ofs_row_argmax of that array, and after every call it is the argmax of what the one-shot call
+ * returns on the samples so far.  The ZS_* variants (ofs_debug_set_variant) select the form of both
+ * calls alike.  Outside the guarantee: the SIGN bit of a NaN output (a NaN appears exactly where the
+ * one-shot call has one), and the one-shot call's fp32 window-FFT plans (2 / 3: OFS_C64 with at most
+ * 64 offsets), which are another arithmetic.
+ * STREAM LENGTH.  The state carries samples and the peak, no sums: every output is computed from the
+ * samples of its own chunk of C offsets alone, so nothing degrades with the stream's length.  Only
+ * the sample count n limits it, and that is an int64.
+ * Calls are stream-ordered and never synchronise with the host: consecutive chunks may be enqueued back
+ * to back (two kernels per call: the metric, then one small workgroup per stream that writes the
+ * history, folds the peak and advances the state).  OFS_EINVAL (before any launch): a (in_fmt,
+ * precision) pair other than the three above, n_br other than 1 or 2, N below 64 or no multiple of 64
+ * or beyond LDS, cp < 0, n_bins outside 1..64, a null bin_indices or template_bins, Tc < 0 or above
+ * the limit, Tc = 0 without final, B < 0, a null or misaligned state with B > 0, a null x with
+ * B * Tc > 0, peak_index or peak_value with a null metric and B * Tc > 0.  B = 0 is a valid no-op.
+ * ofs_zc_freq_chunk_state_bytes returns the bytes of ONE stream's state (64 + n_br * (N + C) * sample
+ * bytes, a multiple of 16) and ofs_zc_freq_chunk_max_samples the largest Tc of one call; both return
+ * OFS_EINVAL (< 0) for an unsupported shape.
+ */
+int64_t ofs_zc_freq_chunk_state_bytes(int32_t in_fmt, int32_t n_br, int32_t N, int32_t cp);
+int64_t ofs_zc_freq_chunk_max_samples(int32_t in_fmt, int32_t n_br, int32_t N, int32_t cp);
+int32_t ofs_zc_freq_metric_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t Tc,
+                                 int32_t N, int32_t cp, int32_t precision, int32_t n_bins,
+                                 const int32_t* bin_indices, const double* template_bins,
+                                 double template_energy, void* state, void* metric, int64_t* off0,
+                                 int64_t* peak_index, double* peak_value, int32_t final, void* stream);
+
 /* Partial sums of the zc_freq metric over one group of branches and one group of template bins, so
  * any branch count and any template length reduce to kernels of <= 4 branches x <= 64 bins (the
  * reference loops over every branch and bin, zc_freq.py:85-97).  For off in [0, noff), noff =

@@ -136,6 +136,10 @@ def _declare(lib):
         "ofs_sc_gate": (c_int32, [c_int32, P, c_int64, c_int64, c_double, P, P, P]),
         "ofs_segment_peak": (c_int32, [P, P, c_int64, c_int64, c_int64, c_int64, P, P, P]),
         "ofs_zc_freq_plan": (c_int32, [c_int32, c_int32, c_int64, c_int32, c_int32]),
+        "ofs_zc_freq_chunk_state_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+        "ofs_zc_freq_chunk_max_samples": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+        "ofs_zc_freq_metric_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32,
+                                               c_int32, c_int32, P, P, c_double, P, P, P, P, P, c_int32, P]),
         "ofs_zc_freq_partial": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, P, P, c_int32, P, P]),
         "ofs_zc_freq_finish": (c_int32, [P, c_int64, c_int64, c_double, c_int32, P, P]),

@@ -306,3 +306,135 @@ def peak_index_batched(metric: torch.Tensor):
     _lib.check(_lib.lib().ofs_row_argmax(prec, metric.data_ptr(), B, n, idx.data_ptr(), val.data_ptr(),
                                          _lib.stream_ptr()), "ofs_row_argmax")
     return idx, val
+
+
+# ------------------------------------------------------------------------------------------
+# Resumable chunk-fed metric (include/ofdmsync.h ofs_zc_freq_metric_chunk, csrc/zc_freq_chunk.hip)
+# ------------------------------------------------------------------------------------------
+_CHUNK_FORMATS = {
+    torch.complex64: (_lib.C64, _lib.FP32, torch.float32),
+    torch.complex128: (_lib.C128, _lib.FP64, torch.float64),
+    torch.int16: (_lib.CI16, _lib.FP64, torch.float64),
+}
+
+
+class FrequencyMetricChunked:
+    """Resumable frequency-domain ZC metric with a running peak over B streams that arrive in chunks
+    (``ofs_zc_freq_metric_chunk``): the chunk-fed form of ``compute_frequency_metric_batched`` on its
+    sliding kernels.
+
+    ``dtype`` fixes the sample format and the result: ``torch.complex64`` (fp64 arithmetic, float32
+    metric), ``torch.complex128`` (float64) or ``torch.int16`` (I/Q pairs in a trailing axis of 2,
+    float64).  ``push(chunk)`` takes the next ``Tc`` samples of every stream - ``[B, n_branch, Tc]``
+    (int16: ``[B, n_branch, Tc, 2]``), or without the branch axis for one branch - and returns the metric
+    ``[B, Tc]`` on the device: element j belongs to the stream's newest sample n = n_seen + j, that is to
+    offset s = n - (N + cp) + 1, the first offset whose window is complete; elements with s < 0 are +0.0.
+    After a push ``off0`` ([B] int64) holds the s of element 0 and ``peak_index`` / ``peak_value`` ([B]
+    int64 / float64) the running ``argmax(metric)`` of each stream over the offsets so far (the
+    reference's detection, zc_freq.py:144; -1 and 0.0 while a stream has no output), found on the
+    device as the chunks pass.  ``push(..., want_metric=False)`` only takes the samples in (returns None;
+    the peak does not advance).  ``push(x, final=True)`` or ``flush()`` leaves fresh streams.  The
+    returned metric is a view of this object's one output buffer (as large as the largest push so far),
+    overwritten in stream order by the next ``push`` that returns a metric, as ``off0`` and the peak
+    tensors are by every push: clone what must outlive it.  ``push`` never synchronises.
+
+    For any chunking of a stream of T >= N + cp samples, the concatenated outputs with their first
+    N + cp - 1 elements dropped equal, bit for bit, the one-shot batched call on the whole stream
+    (complex64: for more than 64 offsets, where the one-shot call runs the sliding kernel too), and the
+    last peak is ``peak_index_batched`` of it.  Nothing is summed across calls, so a stream may be of any
+    length.  ``N`` / ``cp`` default to the module globals ``N_FFT`` / ``CYCLIC_PREFIX`` read at
+    construction, the template to ``make_pss_frequency_template()``; all are fixed for the object's life.
+    Shapes: N a multiple of 64 (>= 64), one or two branches, 1..64 template bins.
+    """
+
+    def __init__(self, B: int, n_branch: int = 1, *, dtype=torch.complex64, N: int | None = None,
+                 cp: int | None = None, bin_indices=None, template_bins=None, template_energy=None, device=None):
+        if dtype not in _CHUNK_FORMATS:
+            raise ValueError(f"dtype must be torch.complex64, torch.complex128 or torch.int16, got {dtype!r}")
+        if bin_indices is None:
+            bin_indices, template_bins, template_energy = make_pss_frequency_template()
+        N = int(N_FFT if N is None else N)
+        cp = int(CYCLIC_PREFIX if cp is None else cp)
+        idx = np.ascontiguousarray(np.asarray(bin_indices).reshape(-1).astype(np.int32))
+        tb = np.ascontiguousarray(np.asarray(template_bins, dtype=np.complex128).reshape(-1))
+        if np.asarray(bin_indices).ndim != 1 or tb.shape != idx.shape or not 0 < idx.size <= MAX_GROUP_BINS:
+            raise ValueError("bin_indices and template_bins must be 1-D of equal length (1..64)")
+        dev = torch.device(device) if device is not None else _lib.require_gpu()
+        lib = _lib.lib()
+        self.fmt, self.precision, self._rdt = _CHUNK_FORMATS[dtype]
+        nbytes = int(lib.ofs_zc_freq_chunk_state_bytes(self.fmt, int(n_branch), N, cp))
+        if nbytes < 0 or B < 0:
+            raise ValueError(f"FrequencyMetricChunked needs n_branch of 1 or 2, N >= 64 a multiple of 64 (blocks "
+                             f"within LDS) and cp >= 0 (got n_branch={n_branch}, N={N}, cp={cp}, dtype={dtype}, B={B})")
+        self.B, self.n_branch, self.N, self.cp, self.dtype, self.device = int(B), int(n_branch), N, cp, dtype, dev
+        self.max_chunk = int(lib.ofs_zc_freq_chunk_max_samples(self.fmt, self.n_branch, N, cp))
+        self._idx, self._tb, self._energy = idx, tb, float(template_energy)
+        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
+        self.n_seen = 0                # host count of samples pushed since the last full reset / final call
+        self.off0 = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+        self.peak_index = torch.full((self.B,), -1, dtype=torch.int64, device=dev)
+        self.peak_value = torch.zeros((self.B,), dtype=torch.float64, device=dev)
+        self._fn = lib.ofs_zc_freq_metric_chunk
+        self._buf = None               # one metric buffer, grown to the largest B * Tc pushed so far
+
+    def _call(self, x, Tc: int, final: bool, want_metric: bool):
+        m = None
+        if want_metric and Tc:
+            if self._buf is None or self._buf.numel() < self.B * Tc:
+                self._buf = torch.empty((self.B * Tc,), dtype=self._rdt, device=self.device)
+            m = self._buf[:self.B * Tc].view(self.B, Tc)
+        track = m is not None or Tc == 0                   # the peak outputs need the metric (a flush reports them)
+        rc = self._fn(self.fmt, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.N, self.cp,
+                      self.precision, int(self._idx.size), self._idx.ctypes.data, self._tb.ctypes.data, self._energy,
+                      self.state.data_ptr(), _lib.ptr(m), self.off0.data_ptr(),
+                      self.peak_index.data_ptr() if track else None, self.peak_value.data_ptr() if track else None,
+                      int(bool(final)), _lib.stream_ptr())
+        _lib.check(rc, "ofs_zc_freq_metric_chunk")
+        self.n_seen = 0 if final else self.n_seen + Tc
+        return m
+
+    def _chunk(self, x, final: bool):
+        """Validate one chunk (before any library call): the contiguous device tensor and its Tc."""
+        iq = (2,) if self.dtype == torch.int16 else ()
+        tail = ", 2" if iq else ""
+        what = (f"[{self.B}, {self.n_branch}, Tc{tail}] {self.dtype}" +
+                (f" (or [{self.B}, Tc{tail}])" if self.n_branch == 1 else ""))
+        if not isinstance(x, torch.Tensor) or x.dtype != self.dtype:
+            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
+        if x.dim() == 2 + len(iq) and self.n_branch == 1:
+            x = x[:, None]
+        if (x.dim() != 3 + len(iq) or x.shape[0] != self.B or x.shape[1] != self.n_branch or
+                tuple(x.shape[3:]) != iq):
+            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
+        Tc = int(x.shape[2])
+        if Tc > self.max_chunk:
+            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
+        if Tc == 0 and not final:
+            raise ValueError("an empty chunk is only valid with final=True (or flush())")
+        if x.device != self.device:
+            x = x.to(self.device)
+        return x.contiguous(), Tc
+
+    def push(self, chunk: torch.Tensor, *, final: bool = False, want_metric: bool = True):
+        """The next chunk of every stream -> metric [B, Tc] (None without ``want_metric`` or for an empty
+        final chunk); ``final=True`` also ends the streams (fresh afterwards)."""
+        x, Tc = self._chunk(chunk, final)
+        return self._call(x, Tc, final, want_metric)
+
+    def flush(self) -> None:
+        """End the streams without new samples (``off0`` and the peak are written once more); the streams
+        are fresh afterwards."""
+        self._call(None, 0, True, False)
+
+    def reset(self, rows=None) -> None:
+        """Make all streams fresh, or the streams ``rows`` (indices, or a bool mask [B]); stream-ordered,
+        no synchronisation.  ``n_seen`` restarts only on a full reset."""
+        if rows is None:
+            self.state.zero_()
+            self.n_seen = 0
+            return
+        r = torch.as_tensor(rows)
+        if r.dtype == torch.bool:
+            self.state.masked_fill_(r.to(self.device)[:, None], 0)
+        else:
+            self.state.index_fill_(0, r.to(self.device, torch.int64), 0)

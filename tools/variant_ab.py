@@ -1,7 +1,7 @@
 """Interleaved A/B of the library's runtime debug variants (ofs_debug_set_variant) over
 tools/bench_configs.py configs, one process, same buffers per config call.  Diagnostic only.
 
-    python tools/variant_ab.py --configs zc_freq_refshape --rounds 3 --variants "base" "ZS_DEFER=1" "ZS_C=256"
+    python tools/variant_ab.py --configs zc_freq_refshape --rounds 3 --variants "base" "ZS_PAIR=0" "ZS_C=256"
 A variant spec is "base" (nothing forced) or comma-separated NAME=VALUE pairs.
 """
 import argparse
