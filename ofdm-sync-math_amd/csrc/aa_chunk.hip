@@ -21,7 +21,7 @@
 // State of one stream (ofs_aa_chunk_state_bytes = 128 + 16·n_ant·L bytes, all-zero = fresh):
 //   AaChunkHdr (128 B), then two history slots [2][n_ant][2L] int32 words.  A call reads slot
 //   `parity` and writes the other one, so no word is overwritten before it is read.
-#include "ofs_common.h"
+#include "chunk_state.h"
 #include "aa_gate.h"
 #include "aa_words.h"
 #include "ofdmsync.h"
@@ -310,9 +310,8 @@ int32_t ofs_aa_detect_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_
                             int32_t detect, double threshold, int32_t hysteresis, double sample_rate,
                             int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_real,
                             int32_t final, void* stream) {
-    if ((in_fmt != OFS_CI16 && in_fmt != OFS_CP12) || !chunk_shape_ok(n_ant, L) || B < 0 || Tc < 0 ||
-        Tc > ofs_aa_chunk_max_samples(n_ant, L) || (Tc == 0 && !final) || OFS_MISSING(state, B) ||
-        (reinterpret_cast<uintptr_t>(state) & 15) != 0 || OFS_MISSING(x, B * Tc) ||
+    if ((in_fmt != OFS_CI16 && in_fmt != OFS_CP12) || !chunk_shape_ok(n_ant, L) ||
+        ofs_chunk::chunk_args_bad(B, Tc, ofs_aa_chunk_max_samples(n_ant, L), final, state, x) ||
         hysteresis > OFS_AA_CHUNK_MAX_HYSTERESIS)
         return OFS_EINVAL;
     if (detect && (OFS_MISSING(n_events, B) || max_events < 0 || (max_events > 0 && B > 0 && (!ev_int || !ev_real))))

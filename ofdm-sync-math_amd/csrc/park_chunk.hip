@@ -29,12 +29,11 @@
 //
 // State of one stream (ofs_park_chunk_state_bytes = 64 + n_br·Hr·sample_bytes, all-zero = fresh):
 // ParkChunkHdr (64 B), then the ring [n_br][Hr] in the input format.  There are no carried sums.
-#include <type_traits>
-#include "ofs_common.h"
-#include "ofdmsync.h"
+#include "chunk_state.h"
 #include "park_tile.h"
 
 using namespace ofs_tile;
+using namespace ofs_chunk;
 
 namespace {
 
@@ -60,7 +59,6 @@ struct ParkChunkArgs {
 constexpr int64_t PC_MAX_TC = (int64_t)1 << 30;
 constexpr int PC_UW = 256;                                  // threads of the update kernel
 
-__host__ __device__ constexpr int pc_sample_bytes(int fmt) { return fmt == OFS_C64 ? 8 : fmt == OFS_C128 ? 16 : 4; }
 __host__ __device__ constexpr int pc_ring(int half) { return (2 * half + 2 * OPT + 3) & ~3; }
 
 // ------------------------------------------------------------------------------------------
@@ -101,9 +99,7 @@ __global__ __launch_bounds__(CW) void park_chunk_kernel(ParkChunkArgs a) {
         if (g >= n_seen) {
             if (g < n_end) v = ld_c<FMT, R>(a.x, (b * nb + br) * Tc + (g - n_seen));
         } else if (g >= 0 && g >= n_seen - Hr) {
-            int s = r0 + (int)(g - n_seen);                  // in (-Hr, Hr)
-            if (s < 0) s += Hr;
-            v = ld_c<FMT, R>(ring, (int64_t)br * Hr + s);
+            v = ld_c<FMT, R>(ring, (int64_t)br * Hr + ring_slot(r0, g - n_seen, Hr));
         }
         return v;
     };
@@ -113,76 +109,38 @@ __global__ __launch_bounds__(CW) void park_chunk_kernel(ParkChunkArgs a) {
 // ------------------------------------------------------------------------------------------
 // update kernel: one workgroup per stream, after the metric kernel
 // ------------------------------------------------------------------------------------------
-// running first argmax (np.argmax: the first maximal element; the first NaN wins once one appears)
-struct Peak { double v; int64_t d; int kind; };
-__device__ __forceinline__ bool peak_beats(const Peak& o, const Peak& m) {     // o replaces m
-    if (o.kind == 0) return false;
-    if (m.kind == 0) return true;
-    if (o.kind != m.kind) return o.kind == 2;
-    if (o.kind == 2) return o.d < m.d;
-    return o.v > m.v || (o.v == m.v && o.d < m.d);
-}
-
 template <int FMT, class R>
 __global__ __launch_bounds__(PC_UW) void park_chunk_update_kernel(ParkChunkArgs a) {
-    using S = typename std::conditional<FMT == OFS_C64, float2, typename std::conditional<FMT == OFS_C128, double2, short2>::type>::type;
-    __shared__ Peak wp[PC_UW / 64];
     const int t = threadIdx.x;
     const int64_t b = blockIdx.x;
     const int64_t Tc = a.Tc;
-    const int half = a.half, Hr = a.Hr;
+    const int half = a.half;
     uint8_t* sp = a.state + b * a.state_bytes;
     ParkChunkHdr* hdr = reinterpret_cast<ParkChunkHdr*>(sp);
     const ParkChunkHdr h = *hdr;
     const int64_t n_seen = h.n_seen;
 
-    if (!a.fin) {                                            // the newest min(Tc, Hr) samples into the ring
-        S* ring = reinterpret_cast<S*>(sp + sizeof(ParkChunkHdr));
-        const int64_t cnt = Tc < Hr ? Tc : Hr;
-        const int r0 = (int)((n_seen + Tc - cnt) % Hr);
-        for (int br = 0; br < a.nb; ++br) {
-            const S* xs = reinterpret_cast<const S*>(a.x) + (b * a.nb + br) * Tc + (Tc - cnt);
-            for (int64_t j = t; j < cnt; j += PC_UW) {
-                int s = r0 + (int)j;
-                if (s >= Hr) s -= Hr;
-                ring[(int64_t)br * Hr + s] = xs[j];
-            }
-        }
-    }
+    if (!a.fin) ring_write<FMT, PC_UW>(sp + sizeof(ParkChunkHdr), a.x, b, a.nb, Tc, n_seen, a.Hr, t);
 
     // The peak runs over the outputs the reference has on the samples so far, d <= n - half - 1: the
     // call's newest output (d = n - half) waits in the header until a later sample arrives.
-    Peak me{0.0, 0, 0};
     const R* row = a.M ? reinterpret_cast<const R*>(a.M) + b * Tc : nullptr;
     const int64_t i_first = n_seen - 2 * (int64_t)half + 1;
     const int64_t nz = i_first >= 0 ? 0 : (-i_first < Tc ? -i_first : Tc);
-    if (row) {                                               // this call's valid outputs but the newest
-        for (int64_t j = nz + t; j < Tc - 1; j += PC_UW) {
-            const double v = (double)row[j];
-            const Peak c{v, half + i_first + j, v != v ? 2 : 1};
-            if (peak_beats(c, me)) me = c;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const Peak o{__shfl_xor(me.v, m), __shfl_xor(me.d, m), __shfl_xor(me.kind, m)};
-        if (peak_beats(o, me)) me = o;
-    }
-    if ((t & 63) == 0) wp[t >> 6] = me;
-    __syncthreads();                                         // also: every thread has read the header
+    ChunkPeak me{0.0, 0, 0};
+    if (row) me = row_peak<PC_UW, 1>(row, nz, Tc - 1, half + i_first, t);     // this call's valid outputs but the newest
+    ChunkPeak pk{h.peak_v, h.peak_d, h.peak_kind};
+    const ChunkPeak pend{h.pend_v, n_seen - half, h.pend_kind};
+    if (Tc > 0 && peak_beats(pend, pk)) pk = pend;
+    pk = peak_fold<PC_UW>(me, pk, t);
     if (t == 0) {
-        Peak pk{h.peak_v, h.peak_d, h.peak_kind};
-        const Peak pend{h.pend_v, n_seen - half, h.pend_kind};
-        if (Tc > 0 && peak_beats(pend, pk)) pk = pend;
-        for (int w = 0; w < PC_UW / 64; ++w)
-            if (peak_beats(wp[w], pk)) pk = wp[w];
         if (a.d0) a.d0[b] = n_seen - half + 1;
-        if (a.peak_index) a.peak_index[b] = pk.kind ? pk.d : -1;
+        if (a.peak_index) a.peak_index[b] = pk.kind ? pk.i : -1;
         if (a.peak_value) a.peak_value[b] = pk.kind ? pk.v : 0.0;
         ParkChunkHdr o{};                                    // final: fresh again (the ring is not read)
         if (!a.fin) {
             o.n_seen = n_seen + Tc;
-            o.peak_d = pk.d; o.peak_v = pk.v; o.peak_kind = pk.kind;
+            o.peak_d = pk.i; o.peak_v = pk.v; o.peak_kind = pk.kind;
             if (row && Tc - 1 >= nz) {                       // (not final, so Tc >= 1)
                 const double v = (double)row[Tc - 1];
                 o.pend_v = v; o.pend_kind = v != v ? 2 : 1;
@@ -227,7 +185,7 @@ extern "C" {
 
 int64_t ofs_park_chunk_state_bytes(int32_t in_fmt, int32_t n_br, int32_t N) {
     if (!shape_ok(in_fmt, n_br, N)) return OFS_EINVAL;
-    return (int64_t)sizeof(ParkChunkHdr) + (int64_t)n_br * pc_ring(N / 2) * pc_sample_bytes(in_fmt);
+    return (int64_t)sizeof(ParkChunkHdr) + (int64_t)n_br * pc_ring(N / 2) * sample_bytes(in_fmt);
 }
 
 int64_t ofs_park_chunk_max_samples(int32_t in_fmt, int32_t n_br, int32_t N) {
@@ -240,9 +198,8 @@ int32_t ofs_park_metric_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t 
                               void* M, void* P, void* E, int64_t* d0,
                               int64_t* peak_index, double* peak_value,
                               int32_t final, void* stream) {
-    if (!shape_ok(in_fmt, n_br, N) || precision != pair_precision(in_fmt) || B < 0 || Tc < 0 || Tc > PC_MAX_TC ||
-        (Tc == 0 && !final) || OFS_MISSING(state, B) || (reinterpret_cast<uintptr_t>(state) & 15) != 0 ||
-        OFS_MISSING(x, B * Tc) || (!M && (peak_index || peak_value) && B * Tc > 0))
+    if (!shape_ok(in_fmt, n_br, N) || precision != pair_precision(in_fmt) ||
+        chunk_args_bad(B, Tc, PC_MAX_TC, final, state, x) || (!M && (peak_index || peak_value) && B * Tc > 0))
         return OFS_EINVAL;
     if (B == 0) return OFS_OK;
     ParkChunkArgs a{};

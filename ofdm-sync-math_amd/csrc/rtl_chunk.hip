@@ -32,7 +32,7 @@
 // State of one stream (ofs_rtl_chunk_state_bytes = 128 + 24·n_br·Q bytes, all-zero = fresh):
 //   RtlChunkHdr (128 B), then two history slots [2][n_br][3Q] int32 words.  A call reads slot
 //   `parity` and writes the other one, so no word is overwritten before it is read.
-#include "ofs_common.h"
+#include "chunk_state.h"
 #include "aa_gate.h"
 #include "aa_words.h"
 #include "rtl_smooth.h"
@@ -540,9 +540,8 @@ int32_t ofs_minn_rtl_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_b
                            double* corr_scaled, double* energy_scaled, uint8_t* metric_valid, uint8_t* above_threshold,
                            int32_t detect, int32_t hysteresis, int32_t timing_offset, int32_t max_events,
                            int32_t* n_events, int64_t* events, int64_t* open_gate_start, int32_t final, void* stream) {
-    if ((in_fmt != OFS_CI16 && in_fmt != OFS_CP12) || !rtl_chunk_shape_ok(n_br, Q) || B < 0 || Tc < 0 ||
-        Tc > ofs_rtl_chunk_max_samples(n_br, Q) || (Tc == 0 && !final) || OFS_MISSING(state, B) ||
-        (reinterpret_cast<uintptr_t>(state) & 15) != 0 || OFS_MISSING(x, B * Tc))
+    if ((in_fmt != OFS_CI16 && in_fmt != OFS_CP12) || !rtl_chunk_shape_ok(n_br, Q) ||
+        ofs_chunk::chunk_args_bad(B, Tc, ofs_rtl_chunk_max_samples(n_br, Q), final, state, x))
         return OFS_EINVAL;
     if (smooth_shift < 0 || smooth_shift > 62 || threshold_frac_bits < 0 || threshold_frac_bits > 62 ||
         (smooth_mode != 0 && smooth_mode != 1) || hysteresis < 0 || hysteresis > OFS_RTL_CHUNK_MAX_HYSTERESIS)

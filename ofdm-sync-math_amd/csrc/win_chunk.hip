@@ -36,7 +36,7 @@
 // State of one stream (ofs_win_chunk_state_bytes = 64 + 2·n_br·(HR + 2·MW + 1)·RL·8 bytes, all-zero =
 // fresh): WinChunkHdr (64 B), then two history slots [2][n_br][(HR + 2·MW + 1)·RL] complex64.  A call
 // reads slot `parity` and writes the other one, so no word is overwritten before it is read.
-#include "ofs_common.h"
+#include "chunk_state.h"
 #include "ofdmsync.h"
 
 using namespace ofs;
@@ -409,8 +409,7 @@ int32_t ofs_win_metric_chunk(int32_t kind, const void* x, int64_t B, int32_t n_b
                              int32_t symbol_len, void* state, void* M, void* P, void* R,
                              int64_t* d0, int32_t final, void* stream) {
     const int plan = chunk_plan(kind, n_br, symbol_len);
-    if (!plan || B < 0 || Tc < 0 || Tc > WC_MAX_TC || (Tc == 0 && !final) || OFS_MISSING(state, B) ||
-        (reinterpret_cast<uintptr_t>(state) & 15) != 0 || OFS_MISSING(x, B * Tc))
+    if (!plan || ofs_chunk::chunk_args_bad(B, Tc, WC_MAX_TC, final, state, x))
         return OFS_EINVAL;
     if (B == 0) return OFS_OK;
     if ((B + WC_WG / 64 - 1) / (WC_WG / 64) > 0x7fffffffll) return OFS_EINVAL;

@@ -31,7 +31,7 @@
 // State of one stream (ofs_zc_chunk_state_bytes = 64 + 8 W rounded up to 16, all-zero = fresh):
 //   ZcChunkHdr (64 B), then the ring double[W] (the next sample's slot is n_seen mod W).  A state row is read and written only by the workgroup
 //   that owns the stream.
-#include "ofs_common.h"
+#include "chunk_state.h"
 #include "ofdmsync.h"
 #include "zc_tiles.h"
 
@@ -385,12 +385,11 @@ int32_t ofs_zc_detect_chunk(const double* corr_mag, int64_t ld_mag, int64_t B, i
                             int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_peak,
                             int64_t* open_gate_start, int32_t final, void* stream) {
     const int64_t sb = ofs_zc_chunk_state_bytes(window_size);
-    if (B < 0 || Tc < 0 || (Tc == 0 && !final) || (B > 1 && ld_mag < Tc) || sb < 0 ||
+    if (ofs_chunk::chunk_args_bad(B, Tc, INT64_MAX, final, state, corr_mag) || (B > 1 && ld_mag < Tc) || sb < 0 ||
         thresh_frac_bits < 0 || thresh_frac_bits > 62 || hysteresis < 0 ||
         hysteresis > OFS_ZC_CHUNK_MAX_HYSTERESIS || max_events < 0)
         return OFS_EINVAL;
-    if (OFS_MISSING(state, B) || (reinterpret_cast<uintptr_t>(state) & 15) != 0 ||
-        (B > 0 && Tc > 0 && !corr_mag) || (reinterpret_cast<uintptr_t>(corr_mag) & 7) != 0 ||
+    if ((reinterpret_cast<uintptr_t>(corr_mag) & 7) != 0 ||
         OFS_MISSING(n_events, B) || OFS_MISSING(open_gate_start, B) ||
         (max_events > 0 && B > 0 && (!ev_int || !ev_peak)))
         return OFS_EINVAL;

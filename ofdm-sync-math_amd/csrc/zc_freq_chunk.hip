@@ -28,8 +28,9 @@
 //
 // State of one stream (ofs_zc_freq_chunk_state_bytes = 64 + n_br·Hr·sample_bytes, all-zero = fresh):
 // ZfcHdr (64 B), then the ring [n_br][Hr] in the input format.  There are no carried sums.
-#include <type_traits>
 #include "zs_body.h"
+
+using namespace ofs_chunk;
 
 namespace {
 
@@ -54,7 +55,6 @@ constexpr int64_t ZFC_MAX_TC = (int64_t)1 << 30;
 constexpr int ZFC_UW = 1024;                                // threads of the update kernel
 constexpr int ZFC_UL = 8;                                   // metric loads in flight per thread of its peak fold
 
-__host__ __device__ constexpr int zfc_sample_bytes(int fmt) { return fmt == OFS_C64 ? 8 : fmt == OFS_C128 ? 16 : 4; }
 // ring length: the N + C - 2 samples before a call that its outputs may read, rounded up to N + C
 __host__ __device__ constexpr int zfc_ring(int N, int C) { return N + C; }
 
@@ -105,83 +105,32 @@ __global__ __launch_bounds__(64 * ZS_MAXW) void zfc_kernel(ZfcArgs q) {
 // ------------------------------------------------------------------------------------------
 // update kernel: one workgroup per stream, after the metric kernel
 // ------------------------------------------------------------------------------------------
-// running first argmax (np.argmax: the first maximal element; the first NaN wins once one appears)
-struct Peak { double v; int64_t s; int kind; };
-__device__ __forceinline__ bool peak_beats(const Peak& o, const Peak& m) {     // o replaces m
-    if (o.kind == 0) return false;
-    if (m.kind == 0) return true;
-    if (o.kind != m.kind) return o.kind == 2;
-    if (o.kind == 2) return o.s < m.s;
-    return o.v > m.v || (o.v == m.v && o.s < m.s);
-}
-
 template <int FMT, class OUT>
 __global__ __launch_bounds__(ZFC_UW) void zfc_update_kernel(ZfcArgs q) {
-    using S = typename std::conditional<FMT == OFS_C64, float2, typename std::conditional<FMT == OFS_C128, double2, short2>::type>::type;
-    __shared__ Peak wp[ZFC_UW / 64];
     const int t = threadIdx.x;
     const int64_t b = blockIdx.x;
     const int64_t Tc = q.Tc;
-    const int Hr = q.Hr;
     uint8_t* sp = q.state + b * q.state_bytes;
     ZfcHdr* hdr = reinterpret_cast<ZfcHdr*>(sp);
     const ZfcHdr h = *hdr;
     const int64_t n_seen = h.n_seen;
 
-    if (!q.fin) {                                            // the newest min(Tc, Hr) samples into the ring
-        S* ring = reinterpret_cast<S*>(sp + sizeof(ZfcHdr));
-        const int64_t cnt = Tc < Hr ? Tc : Hr;
-        const int r0 = (int)((n_seen + Tc - cnt) % Hr);
-        for (int br = 0; br < q.nb; ++br) {
-            const S* xs = reinterpret_cast<const S*>(q.z.x) + (b * q.nb + br) * Tc + (Tc - cnt);
-            for (int64_t j = t; j < cnt; j += ZFC_UW) {
-                int s = r0 + (int)j;
-                if (s >= Hr) s -= Hr;
-                ring[(int64_t)br * Hr + s] = xs[j];
-            }
-        }
-    }
+    if (!q.fin) ring_write<FMT, ZFC_UW>(sp + sizeof(ZfcHdr), q.z.x, b, q.nb, Tc, n_seen, q.Hr, t);
 
-    Peak me{0.0, 0, 0};
     const OUT* row = q.z.metric ? static_cast<const OUT*>(q.z.metric) + b * Tc : nullptr;
     const int64_t s_first = n_seen - ((int64_t)q.z.N + q.z.cp) + 1;
     const int64_t nz = s_first >= 0 ? 0 : (-s_first < Tc ? -s_first : Tc);
-    if (row) {                                               // this call's outputs (every one is the reference's)
-        // one workgroup reads the whole row: ZFC_UL independent loads per thread and round, or the
-        // fold waits out one memory latency per element
-        for (int64_t j0 = nz + t; j0 < Tc; j0 += (int64_t)ZFC_UL * ZFC_UW) {
-            double v[ZFC_UL];
-#pragma unroll
-            for (int u = 0; u < ZFC_UL; ++u) {
-                const int64_t j = j0 + (int64_t)u * ZFC_UW;
-                v[u] = j < Tc ? (double)row[j] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < ZFC_UL; ++u) {
-                const int64_t j = j0 + (int64_t)u * ZFC_UW;
-                const Peak c{v[u], s_first + j, j < Tc ? (v[u] != v[u] ? 2 : 1) : 0};
-                if (peak_beats(c, me)) me = c;
-            }
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const Peak o{__shfl_xor(me.v, m), __shfl_xor(me.s, m), __shfl_xor(me.kind, m)};
-        if (peak_beats(o, me)) me = o;
-    }
-    if ((t & 63) == 0) wp[t >> 6] = me;
-    __syncthreads();                                         // also: every thread has read the header
+    ChunkPeak me{0.0, 0, 0};
+    if (row) me = row_peak<ZFC_UW, ZFC_UL>(row, nz, Tc, s_first, t);   // this call's outputs (every one is the reference's)
+    const ChunkPeak pk = peak_fold<ZFC_UW>(me, ChunkPeak{h.peak_v, h.peak_s, h.peak_kind}, t);
     if (t == 0) {
-        Peak pk{h.peak_v, h.peak_s, h.peak_kind};
-        for (int w = 0; w < ZFC_UW / 64; ++w)
-            if (peak_beats(wp[w], pk)) pk = wp[w];
         if (q.off0) q.off0[b] = s_first;
-        if (q.peak_index) q.peak_index[b] = pk.kind ? pk.s : -1;
+        if (q.peak_index) q.peak_index[b] = pk.kind ? pk.i : -1;
         if (q.peak_value) q.peak_value[b] = pk.kind ? pk.v : 0.0;
         ZfcHdr o{};                                          // final: fresh again (the ring is not read)
         if (!q.fin) {
             o.n_seen = n_seen + Tc;
-            o.peak_s = pk.s; o.peak_v = pk.v; o.peak_kind = pk.kind;
+            o.peak_s = pk.i; o.peak_v = pk.v; o.peak_kind = pk.kind;
         }
         *hdr = o;
     }
@@ -234,7 +183,7 @@ extern "C" {
 
 int64_t ofs_zc_freq_chunk_state_bytes(int32_t in_fmt, int32_t n_br, int32_t N, int32_t cp) {
     if (!zfc_shape_ok(in_fmt, n_br, N, cp)) return OFS_EINVAL;
-    return (int64_t)sizeof(ZfcHdr) + (int64_t)n_br * zfc_ring(N, zs_chunk_len(N)) * zfc_sample_bytes(in_fmt);
+    return (int64_t)sizeof(ZfcHdr) + (int64_t)n_br * zfc_ring(N, zs_chunk_len(N)) * sample_bytes(in_fmt);
 }
 
 int64_t ofs_zc_freq_chunk_max_samples(int32_t in_fmt, int32_t n_br, int32_t N, int32_t cp) {
@@ -248,8 +197,7 @@ int32_t ofs_zc_freq_metric_chunk(int32_t in_fmt, const void* x, int64_t B, int32
                                  double template_energy, void* state, void* metric, int64_t* off0,
                                  int64_t* peak_index, double* peak_value, int32_t final, void* stream) {
     if (!zfc_shape_ok(in_fmt, n_br, N, cp) || precision != zfc_precision(in_fmt) || n_bins < 1 || n_bins > 64 ||
-        !bin_indices || !template_bins || B < 0 || Tc < 0 || Tc > ZFC_MAX_TC || (Tc == 0 && !final) ||
-        OFS_MISSING(state, B) || (reinterpret_cast<uintptr_t>(state) & 15) != 0 || OFS_MISSING(x, B * Tc) ||
+        !bin_indices || !template_bins || chunk_args_bad(B, Tc, ZFC_MAX_TC, final, state, x) ||
         (!metric && (peak_index || peak_value) && B * Tc > 0))
         return OFS_EINVAL;
     if (B == 0) return OFS_OK;

@@ -26,8 +26,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <stdint.h>
-#include "ofdmsync.h"
-#include "ofs_common.h"
+#include "chunk_state.h"
 
 namespace {
 
@@ -95,9 +94,7 @@ struct ZsRing {
     __device__ __forceinline__ double2 ld(const ZsArgs&, int64_t r, int64_t i) const {
         if (i >= n_seen) return ldx<FMT>(x, (xrow0 + r) * Tc + (i - n_seen));
         if (i < n_seen - Hr) return make_double2(0.0, 0.0);            // (never read: Hr >= N + C - 2)
-        int s = r0 + (int)(i - n_seen);                                // in (-Hr, Hr)
-        if (s < 0) s += Hr;
-        return ldx<FMT>(ring, r * Hr + s);
+        return ldx<FMT>(ring, r * Hr + ofs_chunk::ring_slot(r0, i - n_seen, Hr));
     }
     __device__ __forceinline__ void ld2(const ZsArgs& a, int r, int64_t i0, int N, double2& p, double2& v) const {
         p = ld(a, r, i0 + N);

@@ -4,7 +4,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _chunked, _lib
 
 _SC, _COMB, _MINN = "sc", "comb", "minn"
 
@@ -79,7 +79,7 @@ class WindowChunkResult:
         self.M, self.P, self.R, self.d0 = M, P, R, d0
 
 
-class WindowMetricChunked:
+class WindowMetricChunked(_chunked.ChunkedStreams):
     """Resumable S&C / combined S&C / Minn timing metric over B complex64 streams that arrive in chunks
     (``ofs_win_metric_chunk``).
 
@@ -102,85 +102,37 @@ class WindowMetricChunked:
     branch); kind, n_branch and symbol_len are fixed for the object's life.
     """
 
+    _entry, _sizes = "ofs_win_metric_chunk", "ofs_win_chunk"
+
     def __init__(self, kind, B: int, n_branch: int = 1, symbol_len: int = 2048,
                  outputs=("M", "P", "R"), device=None):
         if kind not in KINDS:
             raise ValueError(f"kind must be 'sc', 'comb' or 'minn' (or 1, 2, 3), got {kind!r}")
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
         self.kind = KINDS[kind]
-        nbytes = int(lib.ofs_win_chunk_state_bytes(self.kind, int(n_branch), int(symbol_len)))
-        if nbytes < 0 or B < 0:
-            raise ValueError(f"WindowMetricChunked supports 1-2 branches and a window (symbol_len / 2, Minn: "
-                             f"symbol_len / 4) of 128/256/512/1024/2048, 2048 with one branch "
-                             f"(got kind={kind!r}, n_branch={n_branch}, symbol_len={symbol_len}, B={B})")
+        super().__init__(B, device, (self.kind, int(n_branch), int(symbol_len)),
+                         f"WindowMetricChunked supports 1-2 branches and a window (symbol_len / 2, Minn: "
+                         f"symbol_len / 4) of 128/256/512/1024/2048, 2048 with one branch "
+                         f"(got kind={kind!r}, n_branch={n_branch}, symbol_len={symbol_len}, B={B})")
         bad = [o for o in outputs if o not in ("M", "P", "R")]
         if bad:
             raise ValueError(f"outputs may name 'M', 'P' and 'R', got {bad}")
-        self.B, self.n_branch, self.symbol_len, self.device = int(B), int(n_branch), int(symbol_len), dev
-        self.max_chunk = int(lib.ofs_win_chunk_max_samples(self.kind, self.n_branch, self.symbol_len))
+        self.n_branch, self.symbol_len = int(n_branch), int(symbol_len)
         self.outputs = tuple(outputs)
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
-        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
-        self._fn = lib.ofs_win_metric_chunk
-        self._bufs: dict[int, WindowChunkResult] = {}
 
-    def _buffers(self, Tc: int) -> WindowChunkResult:
-        r = self._bufs.get(Tc)
-        if r is None:
-            B, dev, want = self.B, self.device, self.outputs
-            M = torch.empty((B, Tc), dtype=torch.float32, device=dev) if "M" in want and Tc else None
-            P = torch.empty((B, Tc), dtype=torch.complex64, device=dev) if "P" in want and Tc else None
-            R = torch.empty((B, Tc), dtype=torch.float32, device=dev) if "R" in want and Tc else None
-            r = self._bufs[Tc] = WindowChunkResult(M, P, R, torch.zeros((B,), dtype=torch.int64, device=dev))
-        return r
+    def _alloc(self, Tc: int) -> WindowChunkResult:
+        B, dev, want = self.B, self.device, self.outputs
+        M = torch.empty((B, Tc), dtype=torch.float32, device=dev) if "M" in want and Tc else None
+        P = torch.empty((B, Tc), dtype=torch.complex64, device=dev) if "P" in want and Tc else None
+        R = torch.empty((B, Tc), dtype=torch.float32, device=dev) if "R" in want and Tc else None
+        return WindowChunkResult(M, P, R, torch.zeros((B,), dtype=torch.int64, device=dev))
 
-    def _call(self, x, Tc: int, final: bool) -> WindowChunkResult:
-        r = self._buffers(Tc)
-        rc = self._fn(self.kind, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.symbol_len,
-                      self.state.data_ptr(), _lib.ptr(r.M), _lib.ptr(r.P), _lib.ptr(r.R), r.d0.data_ptr(),
-                      int(bool(final)), _lib.stream_ptr())
-        _lib.check(rc, "ofs_win_metric_chunk")
-        self.samples_seen = 0 if final else self.samples_seen + Tc
-        return r
+    def _launch(self, x, Tc: int, final: int, r: WindowChunkResult):
+        return self._fn(self.kind, x, self.B, self.n_branch, Tc, self.symbol_len,
+                        self.state.data_ptr(), _lib.ptr(r.M), _lib.ptr(r.P), _lib.ptr(r.R), r.d0.data_ptr(),
+                        final, _lib.stream_ptr())
 
     def _chunk(self, x, final: bool):
-        """Validate one chunk (before any library call): the contiguous device tensor and its Tc."""
-        what = (f"[{self.B}, {self.n_branch}, Tc] complex64" +
-                (f" (or [{self.B}, Tc])" if self.n_branch == 1 else ""))
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.complex64:
-            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
-        if x.dim() == 2 and self.n_branch == 1:
-            x = x[:, None, :]
-        if x.dim() != 3 or x.shape[0] != self.B or x.shape[1] != self.n_branch:
-            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
-        Tc = int(x.shape[2])
-        if Tc > self.max_chunk:
-            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
-        if Tc == 0 and not final:
-            raise ValueError("an empty chunk is only valid with final=True (or flush())")
-        if x.device != self.device:
-            x = x.to(self.device)
-        return x.contiguous(), Tc
-
-    def push(self, x: torch.Tensor, final: bool = False) -> WindowChunkResult:
-        """The next chunk of every stream; ``final=True`` also ends the streams (fresh afterwards)."""
-        x, Tc = self._chunk(x, final)
-        return self._call(x, Tc, final)
-
-    def flush(self) -> WindowChunkResult:
-        """End the streams without new samples (M, P, R are None); the streams are fresh afterwards."""
-        return self._call(None, 0, True)
-
-    def reset(self, mask: torch.Tensor | None = None) -> None:
-        """Make all streams fresh, or those where ``mask`` [B] (bool) is set (stream-ordered, no
-        synchronisation).  ``samples_seen`` restarts only on a full reset."""
-        if mask is None:
-            self.state.zero_()
-            self.samples_seen = 0
-        else:
-            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
-            self.state.masked_fill_(m[:, None], 0)
+        return _chunked.complex_chunk(self, x, final, self.n_branch, torch.complex64, "complex64")
 
 
 class SCMinnChunked:

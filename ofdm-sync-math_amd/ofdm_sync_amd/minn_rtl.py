@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _chunked, _lib
 
 N_FFT = 2048                                   # core.py:6
 SMOOTH_SHIFT = 3                               # minn_rtl.py:831
@@ -185,7 +185,7 @@ _ARRAYS = ("corr_total", "corr_positive", "smooth_metric", "energy_total", "corr
            "metric_valid", "above_threshold")
 
 
-class MinnRTLChunkedDetector:
+class MinnRTLChunkedDetector(_chunked.ChunkedStreams):
     """Resumable RTL Minn detection over B integer streams that arrive in chunks (``ofs_minn_rtl_chunk``).
 
     ``push(x)`` takes the next ``Tc`` samples of every stream - int16 ``[B, n_branch, Tc, 2]``, or packed
@@ -207,95 +207,44 @@ class MinnRTLChunkedDetector:
     parameter is fixed for the detector's life.
     """
 
+    _entry, _sizes = "ofs_minn_rtl_chunk", "ofs_rtl_chunk"
+
     def __init__(self, B: int, quarter_len: int, n_branch: int = 1, *, smooth_shift: int = SMOOTH_SHIFT,
                  threshold_value: int = THRESH_VALUE, threshold_frac_bits: int = THRESH_FRAC_BITS,
                  smooth_mode: str = "float", hysteresis: int = HYSTERESIS, timing_offset: int = TIMING_OFFSET,
                  in_dtype=torch.int16, outputs=_ARRAYS, detect: bool = True, max_events: int = 16, device=None):
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
-        if in_dtype == "cp12":
-            self.fmt = _lib.CP12
-        elif in_dtype == torch.int16:
-            self.fmt = _lib.CI16
-        else:
-            raise ValueError(f'in_dtype must be torch.int16 or "cp12", got {in_dtype!r}')
+        self.fmt = _chunked.word_format(in_dtype)
         unknown = [k for k in outputs if k not in _ARRAYS]
         if unknown:
             raise ValueError(f"unknown outputs {unknown}; choose from {_ARRAYS}")
-        nbytes = int(lib.ofs_rtl_chunk_state_bytes(int(n_branch), int(quarter_len)))
-        if nbytes < 0 or B < 0:
-            raise ValueError(f"MinnRTLChunkedDetector supports 1-2 branches and quarter_len in 64/128/256/512 "
-                             f"(got n_branch={n_branch}, quarter_len={quarter_len}, B={B})")
-        self.B, self.n_branch, self.Q, self.device = int(B), int(n_branch), int(quarter_len), dev
-        self.max_chunk = int(lib.ofs_rtl_chunk_max_samples(self.n_branch, self.Q))
+        super().__init__(B, device, (int(n_branch), int(quarter_len)),
+                         f"MinnRTLChunkedDetector supports 1-2 branches and quarter_len in 64/128/256/512 "
+                         f"(got n_branch={n_branch}, quarter_len={quarter_len}, B={B})")
+        self.n_branch, self.Q = int(n_branch), int(quarter_len)
         self.max_events = max(int(max_events), 1)
         self.detect = bool(detect)
         self.outputs = tuple(outputs)
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
-        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
         self._head = (int(smooth_shift), _SMOOTH_MODES[smooth_mode], int(threshold_value), int(threshold_frac_bits))
         self._gate = (int(detect), int(hysteresis), int(timing_offset), self.max_events)
-        self._fn = lib.ofs_minn_rtl_chunk
-        self._bufs: dict[int, MinnRTLBatch] = {}
 
-    def _buffers(self, Tc: int) -> MinnRTLBatch:
-        r = self._bufs.get(Tc)
-        if r is None:
-            B, dev = self.B, self.device
-            arr = {k: (torch.empty((B, Tc), dtype=torch.bool if k in ("metric_valid", "above_threshold")
-                                   else torch.float64, device=dev) if k in self.outputs and Tc else None)
-                   for k in _ARRAYS}
-            r = MinnRTLBatch(**arr)
-            if self.detect:
-                r.n_events = torch.zeros((B,), dtype=torch.int32, device=dev)
-                r.events = torch.zeros((B, self.max_events, 4), dtype=torch.int64, device=dev)
-                r.open_gate_start = torch.full((B,), -1, dtype=torch.int64, device=dev)
-            self._bufs[Tc] = r
+    def _alloc(self, Tc: int) -> MinnRTLBatch:
+        B, dev = self.B, self.device
+        arr = {k: (torch.empty((B, Tc), dtype=torch.bool if k in ("metric_valid", "above_threshold")
+                               else torch.float64, device=dev) if k in self.outputs and Tc else None)
+               for k in _ARRAYS}
+        r = MinnRTLBatch(**arr)
+        if self.detect:
+            r.n_events = torch.zeros((B,), dtype=torch.int32, device=dev)
+            r.events = torch.zeros((B, self.max_events, 4), dtype=torch.int64, device=dev)
+            r.open_gate_start = torch.full((B,), -1, dtype=torch.int64, device=dev)
         return r
 
-    def _call(self, x, Tc: int, final: bool) -> MinnRTLBatch:
-        r = self._buffers(Tc)
-        rc = self._fn(self.fmt, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.Q,
-                      *self._head, self.state.data_ptr(), *[_lib.ptr(getattr(r, k)) for k in _ARRAYS],
-                      *self._gate, _lib.ptr(r.n_events), _lib.ptr(r.events), _lib.ptr(r.open_gate_start),
-                      int(bool(final)), _lib.stream_ptr())
-        _lib.check(rc, "ofs_minn_rtl_chunk")
-        self.samples_seen = 0 if final else self.samples_seen + Tc
-        return r
+    def _launch(self, x, Tc: int, final: int, r: MinnRTLBatch):
+        return self._fn(self.fmt, x, self.B, self.n_branch, Tc, self.Q,
+                        *self._head, self.state.data_ptr(), *[_lib.ptr(getattr(r, k)) for k in _ARRAYS],
+                        *self._gate, _lib.ptr(r.n_events), _lib.ptr(r.events), _lib.ptr(r.open_gate_start),
+                        final, _lib.stream_ptr())
 
-    def push(self, x: torch.Tensor, final: bool = False) -> MinnRTLBatch:
-        """The next chunk of every stream; ``final=True`` also ends the streams (fresh afterwards)."""
-        if self.fmt == _lib.CP12:
-            ok = x.dtype == torch.uint8 and x.dim() == 3 and x.shape[0] == self.B and x.shape[2] == 3 * self.n_branch
-            Tc = int(x.shape[1]) if ok else 0
-            what = f"[{self.B}, Tc, {3 * self.n_branch}] uint8"
-        else:
-            ok = (x.dtype == torch.int16 and x.dim() == 4 and x.shape[0] == self.B and x.shape[1] == self.n_branch
-                  and x.shape[3] == 2)
-            Tc = int(x.shape[2]) if ok else 0
-            what = f"[{self.B}, {self.n_branch}, Tc, 2] int16"
-        if not ok:
-            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
-        if Tc > self.max_chunk:
-            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk} "
-                             f"(n_branch = {self.n_branch}, quarter_len = {self.Q}); push it in pieces")
-        if Tc == 0 and not final:
-            raise ValueError("an empty chunk is only valid with final=True (or flush())")
-        if x.device != self.device:
-            x = x.to(self.device)
-        return self._call(x.contiguous(), Tc, final)
-
-    def flush(self) -> MinnRTLBatch:
-        """End the streams without new samples: no events, ``open_gate_start`` as carried (the arrays
-        are None); the streams are fresh afterwards."""
-        return self._call(None, 0, True)
-
-    def reset(self, mask: torch.Tensor | None = None) -> None:
-        """Make all streams fresh, or those where ``mask`` [B] (bool) is set (stream-ordered, no
-        synchronisation).  ``samples_seen`` restarts only on a full reset."""
-        if mask is None:
-            self.state.zero_()
-            self.samples_seen = 0
-        else:
-            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
-            self.state.masked_fill_(m[:, None], 0)
+    def _chunk(self, x, final: bool):
+        return _chunked.word_chunk(self, x, final, self.n_branch,
+                                   f" (n_branch = {self.n_branch}, quarter_len = {self.Q})")

@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _chunked, _lib
 
 N_FFT = 2048            # core.py:6
 
@@ -71,7 +71,7 @@ class ParkChunkResult:
         self.peak_index, self.peak_value = peak_index, peak_value
 
 
-class ParkChunkedMetric:
+class ParkChunkedMetric(_chunked.ChunkedStreams):
     """Resumable Park timing metric with a running peak over B streams that arrive in chunks
     (``ofs_park_metric_chunk``).
 
@@ -99,6 +99,8 @@ class ParkChunkedMetric:
     n_branch and dtype are fixed for the object's life.  N is at most 8190 (complex64) or 4094.
     """
 
+    _entry, _sizes = "ofs_park_metric_chunk", "ofs_park_chunk"
+
     def __init__(self, B: int, n_branch: int = 1, N: int | None = None, dtype=torch.complex64,
                  outputs=("M", "P", "E"), track_peak: bool = True, device=None):
         if dtype not in _CHUNK_FORMATS:
@@ -107,84 +109,35 @@ class ParkChunkedMetric:
         if bad:
             raise ValueError(f"outputs may name 'M', 'P' and 'E', got {bad}")
         N = int(N_FFT if N is None else N)
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
         self.fmt, self.precision, self._rdt, self._cdt = _CHUNK_FORMATS[dtype]
-        nbytes = int(lib.ofs_park_chunk_state_bytes(self.fmt, int(n_branch), N))
-        if nbytes < 0 or B < 0:
-            raise ValueError(f"ParkChunkedMetric needs n_branch >= 1 and 2 <= N <= 8190 (complex64) or 4094 "
-                             f"(complex128, int16) (got n_branch={n_branch}, N={N}, dtype={dtype}, B={B})")
-        self.B, self.n_branch, self.N, self.dtype, self.device = int(B), int(n_branch), N, dtype, dev
-        self.max_chunk = int(lib.ofs_park_chunk_max_samples(self.fmt, self.n_branch, N))
+        super().__init__(B, device, (self.fmt, int(n_branch), N),
+                         f"ParkChunkedMetric needs n_branch >= 1 and 2 <= N <= 8190 (complex64) or 4094 "
+                         f"(complex128, int16) (got n_branch={n_branch}, N={N}, dtype={dtype}, B={B})")
+        self.n_branch, self.N, self.dtype = int(n_branch), N, dtype
         self.outputs, self.track_peak = tuple(outputs), bool(track_peak)
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
-        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
-        self._fn = lib.ofs_park_metric_chunk
-        self._bufs: dict[int, tuple] = {}
 
-    def _buffers(self, Tc: int):
-        r = self._bufs.get(Tc)
-        if r is None:
-            B, dev, want = self.B, self.device, self.outputs
-            M = torch.empty((B, Tc), dtype=self._rdt, device=dev) if "M" in want and Tc else None
-            P = torch.empty((B, Tc), dtype=self._cdt, device=dev) if "P" in want and Tc else None
-            E = torch.empty((B, Tc), dtype=self._rdt, device=dev) if "E" in want and Tc else None
-            pi = torch.zeros((B,), dtype=torch.int64, device=dev) if self.track_peak else None
-            pv = torch.zeros((B,), dtype=torch.float64, device=dev) if self.track_peak else None
-            res = ParkChunkResult(M, P, E, torch.zeros((B,), dtype=torch.int64, device=dev), pi, pv)
-            # the peak is folded from M: a private M buffer when the caller did not ask for M
-            Mk = torch.empty((B, Tc), dtype=self._rdt, device=dev) if self.track_peak and M is None and Tc else M
-            r = self._bufs[Tc] = (res, Mk)
-        return r
+    def _alloc(self, Tc: int):
+        """(the result, the M buffer the call writes)."""
+        B, dev, want = self.B, self.device, self.outputs
+        M = torch.empty((B, Tc), dtype=self._rdt, device=dev) if "M" in want and Tc else None
+        P = torch.empty((B, Tc), dtype=self._cdt, device=dev) if "P" in want and Tc else None
+        E = torch.empty((B, Tc), dtype=self._rdt, device=dev) if "E" in want and Tc else None
+        pi = torch.zeros((B,), dtype=torch.int64, device=dev) if self.track_peak else None
+        pv = torch.zeros((B,), dtype=torch.float64, device=dev) if self.track_peak else None
+        res = ParkChunkResult(M, P, E, torch.zeros((B,), dtype=torch.int64, device=dev), pi, pv)
+        # the peak is folded from M: a private M buffer when the caller did not ask for M
+        Mk = torch.empty((B, Tc), dtype=self._rdt, device=dev) if self.track_peak and M is None and Tc else M
+        return res, Mk
+
+    def _launch(self, x, Tc: int, final: int, bufs):
+        r, Mk = bufs
+        return self._fn(self.fmt, x, self.B, self.n_branch, Tc, self.N,
+                        self.precision, self.state.data_ptr(), _lib.ptr(Mk), _lib.ptr(r.P), _lib.ptr(r.E),
+                        r.d0.data_ptr(), _lib.ptr(r.peak_index), _lib.ptr(r.peak_value), final,
+                        _lib.stream_ptr())
 
     def _call(self, x, Tc: int, final: bool) -> ParkChunkResult:
-        r, Mk = self._buffers(Tc)
-        rc = self._fn(self.fmt, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.N,
-                      self.precision, self.state.data_ptr(), _lib.ptr(Mk), _lib.ptr(r.P), _lib.ptr(r.E),
-                      r.d0.data_ptr(), _lib.ptr(r.peak_index), _lib.ptr(r.peak_value), int(bool(final)),
-                      _lib.stream_ptr())
-        _lib.check(rc, "ofs_park_metric_chunk")
-        self.samples_seen = 0 if final else self.samples_seen + Tc
-        return r
+        return super()._call(x, Tc, final)[0]
 
     def _chunk(self, x, final: bool):
-        """Validate one chunk (before any library call): the contiguous device tensor and its Tc."""
-        iq = (2,) if self.dtype == torch.int16 else ()
-        tail = ", 2" if iq else ""
-        what = (f"[{self.B}, {self.n_branch}, Tc{tail}] {self.dtype}" +
-                (f" (or [{self.B}, Tc{tail}])" if self.n_branch == 1 else ""))
-        if not isinstance(x, torch.Tensor) or x.dtype != self.dtype:
-            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
-        if x.dim() == 2 + len(iq) and self.n_branch == 1:
-            x = x[:, None]
-        if (x.dim() != 3 + len(iq) or x.shape[0] != self.B or x.shape[1] != self.n_branch or
-                tuple(x.shape[3:]) != iq):
-            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
-        Tc = int(x.shape[2])
-        if Tc > self.max_chunk:
-            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
-        if Tc == 0 and not final:
-            raise ValueError("an empty chunk is only valid with final=True (or flush())")
-        if x.device != self.device:
-            x = x.to(self.device)
-        return x.contiguous(), Tc
-
-    def push(self, x: torch.Tensor, final: bool = False) -> ParkChunkResult:
-        """The next chunk of every stream; ``final=True`` also ends the streams (fresh afterwards)."""
-        x, Tc = self._chunk(x, final)
-        return self._call(x, Tc, final)
-
-    def flush(self) -> ParkChunkResult:
-        """End the streams without new samples (M, P, E are None; d0 and the peak are written); the
-        streams are fresh afterwards."""
-        return self._call(None, 0, True)
-
-    def reset(self, mask: torch.Tensor | None = None) -> None:
-        """Make all streams fresh, or those where ``mask`` [B] (bool) is set (stream-ordered, no
-        synchronisation).  ``samples_seen`` restarts only on a full reset."""
-        if mask is None:
-            self.state.zero_()
-            self.samples_seen = 0
-        else:
-            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
-            self.state.masked_fill_(m[:, None], 0)
+        return _chunked.complex_chunk(self, x, final, self.n_branch, self.dtype)

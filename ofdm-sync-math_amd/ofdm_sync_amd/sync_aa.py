@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _chunked, _lib
 
 # System constants (sync_aa.py:99-125)
 N_FFT = 1024
@@ -256,7 +256,38 @@ class AABatchDetector:
         return bool(n is not None and n.numel() and int(n.max().item()) > self.max_events)
 
 
-class AAChunkedDetector:
+class _AAChunked(_chunked.ChunkedStreams):
+    """What the two chunked [A][A] detectors share: parameters, result buffers, the call's argument list
+    (``_lead``: the arguments in front of ``x``)."""
+    _out_dtypes = _lead = ()
+
+    def _setup(self, n_ant, L, threshold, hysteresis, sample_rate, outputs, detect, max_events):
+        self.n_ant, self.L = int(n_ant), int(L)
+        self.max_events = max(int(max_events), 1)
+        self.detect = bool(detect)
+        self.outputs = tuple(outputs)
+        self._par = (int(detect), float(threshold), int(hysteresis), float(sample_rate), self.max_events)
+
+    def _alloc(self, Tc: int) -> AABatchResult:
+        B, dev, E, want = self.B, self.device, self.max_events, self.outputs
+        cdt, rdt = self._out_dtypes
+        P, R, M, V = allocate(dev, [((B, Tc), cdt) if "P" in want and Tc else None,
+                                    ((B, Tc), rdt) if "R" in want and Tc else None,
+                                    ((B, Tc), rdt) if "M" in want and Tc else None,
+                                    ((B, Tc), torch.bool) if "valid" in want and Tc else None])
+        n_ev = torch.zeros((B,), dtype=torch.int32, device=dev) if self.detect else None
+        ev_i = torch.zeros((B, E, 4), dtype=torch.int64, device=dev) if self.detect else None
+        ev_r = torch.zeros((B, E, 4), dtype=torch.float64, device=dev) if self.detect else None
+        return AABatchResult(P, R, M, V, n_ev, ev_i, ev_r)
+
+    def _launch(self, x, Tc: int, final: int, r: AABatchResult):
+        return self._fn(*self._lead, x, self.B, self.n_ant, Tc, self.L,
+                        self.state.data_ptr(), _lib.ptr(r.P), _lib.ptr(r.R), _lib.ptr(r.M), _lib.ptr(r.valid),
+                        *self._par, _lib.ptr(r.n_events), _lib.ptr(r.ev_int), _lib.ptr(r.ev_real),
+                        final, _lib.stream_ptr())
+
+
+class AAChunkedDetector(_AAChunked):
     """Resumable [A][A] detection over B integer streams that arrive in chunks (``ofs_aa_detect_chunk``).
 
     ``push(x)`` takes the next ``Tc`` samples of every stream - int16 ``[B, n_ant, Tc, 2]``, or packed
@@ -277,96 +308,25 @@ class AAChunkedDetector:
     L, threshold, hysteresis and n_ant are fixed for the detector's life.
     """
 
+    _entry, _sizes = "ofs_aa_detect_chunk", "ofs_aa_chunk"
+    _out_dtypes = (torch.complex128, torch.float64)
+
     def __init__(self, B: int, n_ant: int = 1, L: int = PREAMBLE_HALF_LEN,
                  threshold: float = DETECT_THRESHOLD, hysteresis: int = DETECT_HYSTERESIS,
                  sample_rate: float = SAMPLE_RATE_HZ, *, in_dtype=torch.int16,
                  outputs=("P", "R", "M"), detect: bool = True, max_events: int = 4, device=None):
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
-        if in_dtype == "cp12":
-            self.fmt = _lib.CP12
-        elif in_dtype == torch.int16:
-            self.fmt = _lib.CI16
-        else:
-            raise ValueError(f'in_dtype must be torch.int16 or "cp12", got {in_dtype!r}')
-        nbytes = int(lib.ofs_aa_chunk_state_bytes(int(n_ant), int(L)))
-        if nbytes < 0 or B < 0:
-            raise ValueError(f"AAChunkedDetector supports 1-2 antennas and L in 64/128/256/512/1024 "
-                             f"(got n_ant={n_ant}, L={L}, B={B})")
-        self.B, self.n_ant, self.L, self.device = int(B), int(n_ant), int(L), dev
-        self.max_chunk = int(lib.ofs_aa_chunk_max_samples(self.n_ant, self.L))
-        self.max_events = max(int(max_events), 1)
-        self.detect = bool(detect)
-        self.outputs = tuple(outputs)
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
-        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
-        self._par = (int(detect), float(threshold), int(hysteresis), float(sample_rate), self.max_events)
-        self._fn = lib.ofs_aa_detect_chunk
-        self._bufs: dict[int, AABatchResult] = {}
+        self.fmt = _chunked.word_format(in_dtype)
+        self._lead = (self.fmt,)
+        super().__init__(B, device, (int(n_ant), int(L)),
+                         f"AAChunkedDetector supports 1-2 antennas and L in 64/128/256/512/1024 "
+                         f"(got n_ant={n_ant}, L={L}, B={B})")
+        self._setup(n_ant, L, threshold, hysteresis, sample_rate, outputs, detect, max_events)
 
-    def _buffers(self, Tc: int) -> AABatchResult:
-        r = self._bufs.get(Tc)
-        if r is None:
-            B, dev, E, want = self.B, self.device, self.max_events, self.outputs
-            P, R, M, V = allocate(dev, [((B, Tc), torch.complex128) if "P" in want and Tc else None,
-                                        ((B, Tc), torch.float64) if "R" in want and Tc else None,
-                                        ((B, Tc), torch.float64) if "M" in want and Tc else None,
-                                        ((B, Tc), torch.bool) if "valid" in want and Tc else None])
-            n_ev = torch.zeros((B,), dtype=torch.int32, device=dev) if self.detect else None
-            ev_i = torch.zeros((B, E, 4), dtype=torch.int64, device=dev) if self.detect else None
-            ev_r = torch.zeros((B, E, 4), dtype=torch.float64, device=dev) if self.detect else None
-            r = self._bufs[Tc] = AABatchResult(P, R, M, V, n_ev, ev_i, ev_r)
-        return r
-
-    def _call(self, x, Tc: int, final: bool) -> AABatchResult:
-        r = self._buffers(Tc)
-        rc = self._fn(self.fmt, None if x is None else x.data_ptr(), self.B, self.n_ant, Tc, self.L,
-                      self.state.data_ptr(), _lib.ptr(r.P), _lib.ptr(r.R), _lib.ptr(r.M), _lib.ptr(r.valid),
-                      *self._par, _lib.ptr(r.n_events), _lib.ptr(r.ev_int), _lib.ptr(r.ev_real),
-                      int(bool(final)), _lib.stream_ptr())
-        _lib.check(rc, "ofs_aa_detect_chunk")
-        self.samples_seen = 0 if final else self.samples_seen + Tc
-        return r
-
-    def push(self, x: torch.Tensor, final: bool = False) -> AABatchResult:
-        """The next chunk of every stream; ``final=True`` also ends the streams (open gates close)."""
-        if self.fmt == _lib.CP12:
-            ok = x.dtype == torch.uint8 and x.dim() == 3 and x.shape[0] == self.B and x.shape[2] == 3 * self.n_ant
-            Tc = int(x.shape[1]) if ok else 0
-            what = f"[{self.B}, Tc, {3 * self.n_ant}] uint8"
-        else:
-            ok = (x.dtype == torch.int16 and x.dim() == 4 and x.shape[0] == self.B and x.shape[1] == self.n_ant
-                  and x.shape[3] == 2)
-            Tc = int(x.shape[2]) if ok else 0
-            what = f"[{self.B}, {self.n_ant}, Tc, 2] int16"
-        if not ok:
-            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
-        if Tc > self.max_chunk:
-            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk} "
-                             f"(n_ant = {self.n_ant}, L = {self.L}); push it in pieces")
-        if Tc == 0 and not final:
-            raise ValueError("an empty chunk is only valid with final=True (or flush())")
-        if x.device != self.device:
-            x = x.to(self.device)
-        return self._call(x.contiguous(), Tc, final)
-
-    def flush(self) -> AABatchResult:
-        """End the streams without new samples: open gates close at the sample count and emit.
-        Events only (P, R, M, valid are None); the streams are fresh afterwards."""
-        return self._call(None, 0, True)
-
-    def reset(self, mask: torch.Tensor | None = None) -> None:
-        """Make all streams fresh, or those where ``mask`` [B] (bool) is set, without closing their
-        gates (stream-ordered, no synchronisation).  ``samples_seen`` restarts only on a full reset."""
-        if mask is None:
-            self.state.zero_()
-            self.samples_seen = 0
-        else:
-            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
-            self.state.masked_fill_(m[:, None], 0)
+    def _chunk(self, x, final: bool):
+        return _chunked.word_chunk(self, x, final, self.n_ant, f" (n_ant = {self.n_ant}, L = {self.L})")
 
 
-class AAChunkedDetectorF32:
+class AAChunkedDetectorF32(_AAChunked):
     """Resumable [A][A] detection over B complex64 streams that arrive in chunks (``ofs_aa_detect_chunk_f32``).
 
     The chunk-fed form of the fp32 fast path (complex64 in, complex64 / float32 out).  ``push(x)`` takes
@@ -387,83 +347,20 @@ class AAChunkedDetectorF32:
     L is 128, 256, 512 or 1024; L, threshold, hysteresis and n_ant are fixed for the detector's life.
     """
 
+    _entry, _sizes = "ofs_aa_detect_chunk_f32", "ofs_aa_chunk_f32"
+    _out_dtypes = (torch.complex64, torch.float32)
+
     def __init__(self, B: int, n_ant: int = 1, L: int = PREAMBLE_HALF_LEN,
                  threshold: float = DETECT_THRESHOLD, hysteresis: int = DETECT_HYSTERESIS,
                  sample_rate: float = SAMPLE_RATE_HZ, *, outputs=("P", "R", "M"), detect: bool = True,
                  max_events: int = 4, device=None):
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
-        nbytes = int(lib.ofs_aa_chunk_f32_state_bytes(int(n_ant), int(L)))
-        if nbytes < 0 or B < 0:
-            raise ValueError(f"AAChunkedDetectorF32 supports 1-2 antennas and L in 128/256/512/1024 "
-                             f"(got n_ant={n_ant}, L={L}, B={B})")
-        self.B, self.n_ant, self.L, self.device = int(B), int(n_ant), int(L), dev
-        self.max_chunk = int(lib.ofs_aa_chunk_f32_max_samples(self.n_ant, self.L))
-        self.max_events = max(int(max_events), 1)
-        self.detect = bool(detect)
-        self.outputs = tuple(outputs)
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
-        self.samples_seen = 0          # host count of samples pushed since the last reset / final call
-        self._par = (int(detect), float(threshold), int(hysteresis), float(sample_rate), self.max_events)
-        self._fn = lib.ofs_aa_detect_chunk_f32
-        self._bufs: dict[int, AABatchResult] = {}
+        super().__init__(B, device, (int(n_ant), int(L)),
+                         f"AAChunkedDetectorF32 supports 1-2 antennas and L in 128/256/512/1024 "
+                         f"(got n_ant={n_ant}, L={L}, B={B})")
+        self._setup(n_ant, L, threshold, hysteresis, sample_rate, outputs, detect, max_events)
 
-    def _buffers(self, Tc: int) -> AABatchResult:
-        r = self._bufs.get(Tc)
-        if r is None:
-            B, dev, E, want = self.B, self.device, self.max_events, self.outputs
-            P, R, M, V = allocate(dev, [((B, Tc), torch.complex64) if "P" in want and Tc else None,
-                                        ((B, Tc), torch.float32) if "R" in want and Tc else None,
-                                        ((B, Tc), torch.float32) if "M" in want and Tc else None,
-                                        ((B, Tc), torch.bool) if "valid" in want and Tc else None])
-            n_ev = torch.zeros((B,), dtype=torch.int32, device=dev) if self.detect else None
-            ev_i = torch.zeros((B, E, 4), dtype=torch.int64, device=dev) if self.detect else None
-            ev_r = torch.zeros((B, E, 4), dtype=torch.float64, device=dev) if self.detect else None
-            r = self._bufs[Tc] = AABatchResult(P, R, M, V, n_ev, ev_i, ev_r)
-        return r
-
-    def _call(self, x, Tc: int, final: bool) -> AABatchResult:
-        r = self._buffers(Tc)
-        rc = self._fn(None if x is None else x.data_ptr(), self.B, self.n_ant, Tc, self.L,
-                      self.state.data_ptr(), _lib.ptr(r.P), _lib.ptr(r.R), _lib.ptr(r.M), _lib.ptr(r.valid),
-                      *self._par, _lib.ptr(r.n_events), _lib.ptr(r.ev_int), _lib.ptr(r.ev_real),
-                      int(bool(final)), _lib.stream_ptr())
-        _lib.check(rc, "ofs_aa_detect_chunk_f32")
-        self.samples_seen = 0 if final else self.samples_seen + Tc
-        return r
-
-    def push(self, x: torch.Tensor, final: bool = False) -> AABatchResult:
-        """The next chunk of every stream; ``final=True`` also ends the streams (open gates close)."""
-        what = f"[{self.B}, {self.n_ant}, Tc] complex64" + (f" (or [{self.B}, Tc])" if self.n_ant == 1 else "")
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.complex64:
-            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
-        if x.dim() == 2 and self.n_ant == 1:
-            x = x[:, None, :]
-        if x.dim() != 3 or x.shape[0] != self.B or x.shape[1] != self.n_ant:
-            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
-        Tc = int(x.shape[2])
-        if Tc > self.max_chunk:
-            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
-        if Tc == 0 and not final:
-            raise ValueError("an empty chunk is only valid with final=True (or flush())")
-        if x.device != self.device:
-            x = x.to(self.device)
-        return self._call(x.contiguous(), Tc, final)
-
-    def flush(self) -> AABatchResult:
-        """End the streams without new samples: open gates close at the sample count and emit.
-        Events only (P, R, M, valid are None); the streams are fresh afterwards."""
-        return self._call(None, 0, True)
-
-    def reset(self, mask: torch.Tensor | None = None) -> None:
-        """Make all streams fresh, or those where ``mask`` [B] (bool) is set, without closing their
-        gates (stream-ordered, no synchronisation).  ``samples_seen`` restarts only on a full reset."""
-        if mask is None:
-            self.state.zero_()
-            self.samples_seen = 0
-        else:
-            m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
-            self.state.masked_fill_(m[:, None], 0)
+    def _chunk(self, x, final: bool):
+        return _chunked.complex_chunk(self, x, final, self.n_ant, torch.complex64, "complex64")
 
 
 def aa_detect_streaming_batched(x, L: int = PREAMBLE_HALF_LEN, threshold: float = DETECT_THRESHOLD,

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _chunked, _lib
 
 N_FFT = 2048            # core.py:6
 CYCLIC_PREFIX = 512     # core.py:8
@@ -318,7 +318,7 @@ _CHUNK_FORMATS = {
 }
 
 
-class FrequencyMetricChunked:
+class FrequencyMetricChunked(_chunked.ChunkedStreams):
     """Resumable frequency-domain ZC metric with a running peak over B streams that arrive in chunks
     (``ofs_zc_freq_metric_chunk``): the chunk-fed form of ``compute_frequency_metric_batched`` on its
     sliding kernels.
@@ -347,6 +347,8 @@ class FrequencyMetricChunked:
     Shapes: N a multiple of 64 (>= 64), one or two branches, 1..64 template bins.
     """
 
+    _entry, _sizes = "ofs_zc_freq_metric_chunk", "ofs_zc_freq_chunk"
+
     def __init__(self, B: int, n_branch: int = 1, *, dtype=torch.complex64, N: int | None = None,
                  cp: int | None = None, bin_indices=None, template_bins=None, template_energy=None, device=None):
         if dtype not in _CHUNK_FORMATS:
@@ -359,61 +361,38 @@ class FrequencyMetricChunked:
         tb = np.ascontiguousarray(np.asarray(template_bins, dtype=np.complex128).reshape(-1))
         if np.asarray(bin_indices).ndim != 1 or tb.shape != idx.shape or not 0 < idx.size <= MAX_GROUP_BINS:
             raise ValueError("bin_indices and template_bins must be 1-D of equal length (1..64)")
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
         self.fmt, self.precision, self._rdt = _CHUNK_FORMATS[dtype]
-        nbytes = int(lib.ofs_zc_freq_chunk_state_bytes(self.fmt, int(n_branch), N, cp))
-        if nbytes < 0 or B < 0:
-            raise ValueError(f"FrequencyMetricChunked needs n_branch of 1 or 2, N >= 64 a multiple of 64 (blocks "
-                             f"within LDS) and cp >= 0 (got n_branch={n_branch}, N={N}, cp={cp}, dtype={dtype}, B={B})")
-        self.B, self.n_branch, self.N, self.cp, self.dtype, self.device = int(B), int(n_branch), N, cp, dtype, dev
-        self.max_chunk = int(lib.ofs_zc_freq_chunk_max_samples(self.fmt, self.n_branch, N, cp))
+        super().__init__(B, device, (self.fmt, int(n_branch), N, cp),
+                         f"FrequencyMetricChunked needs n_branch of 1 or 2, N >= 64 a multiple of 64 (blocks "
+                         f"within LDS) and cp >= 0 (got n_branch={n_branch}, N={N}, cp={cp}, dtype={dtype}, B={B})")
+        self.n_branch, self.N, self.cp, self.dtype = int(n_branch), N, cp, dtype
         self._idx, self._tb, self._energy = idx, tb, float(template_energy)
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)     # all-zero = fresh
-        self.n_seen = 0                # host count of samples pushed since the last full reset / final call
-        self.off0 = torch.zeros((self.B,), dtype=torch.int64, device=dev)
-        self.peak_index = torch.full((self.B,), -1, dtype=torch.int64, device=dev)
-        self.peak_value = torch.zeros((self.B,), dtype=torch.float64, device=dev)
-        self._fn = lib.ofs_zc_freq_metric_chunk
+        self.off0 = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
+        self.peak_index = torch.full((self.B,), -1, dtype=torch.int64, device=self.device)
+        self.peak_value = torch.zeros((self.B,), dtype=torch.float64, device=self.device)
         self._buf = None               # one metric buffer, grown to the largest B * Tc pushed so far
 
-    def _call(self, x, Tc: int, final: bool, want_metric: bool):
-        m = None
-        if want_metric and Tc:
-            if self._buf is None or self._buf.numel() < self.B * Tc:
-                self._buf = torch.empty((self.B * Tc,), dtype=self._rdt, device=self.device)
-            m = self._buf[:self.B * Tc].view(self.B, Tc)
+    # host count of samples pushed since the last full reset / final call (the base's counter)
+    n_seen = property(lambda self: self.samples_seen, lambda self, n: setattr(self, "samples_seen", n))
+
+    def _buffers(self, Tc: int, want_metric: bool):
+        """The metric view of this call (None without one): no cache per ``Tc``, one growing buffer."""
+        if not (want_metric and Tc):
+            return None
+        if self._buf is None or self._buf.numel() < self.B * Tc:
+            self._buf = torch.empty((self.B * Tc,), dtype=self._rdt, device=self.device)
+        return self._buf[:self.B * Tc].view(self.B, Tc)
+
+    def _launch(self, x, Tc: int, final: int, m):
         track = m is not None or Tc == 0                   # the peak outputs need the metric (a flush reports them)
-        rc = self._fn(self.fmt, None if x is None else x.data_ptr(), self.B, self.n_branch, Tc, self.N, self.cp,
-                      self.precision, int(self._idx.size), self._idx.ctypes.data, self._tb.ctypes.data, self._energy,
-                      self.state.data_ptr(), _lib.ptr(m), self.off0.data_ptr(),
-                      self.peak_index.data_ptr() if track else None, self.peak_value.data_ptr() if track else None,
-                      int(bool(final)), _lib.stream_ptr())
-        _lib.check(rc, "ofs_zc_freq_metric_chunk")
-        self.n_seen = 0 if final else self.n_seen + Tc
-        return m
+        return self._fn(self.fmt, x, self.B, self.n_branch, Tc, self.N, self.cp,
+                        self.precision, int(self._idx.size), self._idx.ctypes.data, self._tb.ctypes.data, self._energy,
+                        self.state.data_ptr(), _lib.ptr(m), self.off0.data_ptr(),
+                        self.peak_index.data_ptr() if track else None, self.peak_value.data_ptr() if track else None,
+                        final, _lib.stream_ptr())
 
     def _chunk(self, x, final: bool):
-        """Validate one chunk (before any library call): the contiguous device tensor and its Tc."""
-        iq = (2,) if self.dtype == torch.int16 else ()
-        tail = ", 2" if iq else ""
-        what = (f"[{self.B}, {self.n_branch}, Tc{tail}] {self.dtype}" +
-                (f" (or [{self.B}, Tc{tail}])" if self.n_branch == 1 else ""))
-        if not isinstance(x, torch.Tensor) or x.dtype != self.dtype:
-            raise ValueError(f"chunk must be {what}, got dtype {getattr(x, 'dtype', type(x))}")
-        if x.dim() == 2 + len(iq) and self.n_branch == 1:
-            x = x[:, None]
-        if (x.dim() != 3 + len(iq) or x.shape[0] != self.B or x.shape[1] != self.n_branch or
-                tuple(x.shape[3:]) != iq):
-            raise ValueError(f"chunk must be {what}, got {tuple(x.shape)} {x.dtype}")
-        Tc = int(x.shape[2])
-        if Tc > self.max_chunk:
-            raise ValueError(f"chunk of {Tc} samples exceeds max_chunk = {self.max_chunk}; push it in pieces")
-        if Tc == 0 and not final:
-            raise ValueError("an empty chunk is only valid with final=True (or flush())")
-        if x.device != self.device:
-            x = x.to(self.device)
-        return x.contiguous(), Tc
+        return _chunked.complex_chunk(self, x, final, self.n_branch, self.dtype)
 
     def push(self, chunk: torch.Tensor, *, final: bool = False, want_metric: bool = True):
         """The next chunk of every stream -> metric [B, Tc] (None without ``want_metric`` or for an empty
@@ -429,12 +408,8 @@ class FrequencyMetricChunked:
     def reset(self, rows=None) -> None:
         """Make all streams fresh, or the streams ``rows`` (indices, or a bool mask [B]); stream-ordered,
         no synchronisation.  ``n_seen`` restarts only on a full reset."""
-        if rows is None:
-            self.state.zero_()
-            self.n_seen = 0
-            return
-        r = torch.as_tensor(rows)
-        if r.dtype == torch.bool:
-            self.state.masked_fill_(r.to(self.device)[:, None], 0)
+        r = None if rows is None else torch.as_tensor(rows)
+        if r is None or r.dtype == torch.bool:
+            super().reset(r)
         else:
             self.state.index_fill_(0, r.to(self.device, torch.int64), 0)

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _chunked, _lib
 
 N_FFT = 2048                                  # core.py:6
 CYCLIC_PREFIX = 512                           # core.py:8
@@ -408,7 +408,7 @@ class ZCChunkResult:
     tail: "ZCChunkResult | None" = None
 
 
-class ZCChunkedDetector:
+class ZCChunkedDetector(_chunked.ChunkedStreams):
     """Resumable zc_v2 detection over B streams that arrive in chunks (``ofs_zc_detect_chunk``).
 
     ``push_mag(corr_mag)`` takes the next ``Tc`` magnitudes of every stream, ``push(x)`` the next
@@ -444,25 +444,26 @@ class ZCChunkedDetector:
     ``n_events[b]`` are not written by a call.  The parameters are fixed for the detector's life.
     """
 
+    _entry, _sizes = "ofs_zc_detect_chunk", "ofs_zc_chunk"
+
     def __init__(self, B: int, reference=None, n_branch: int = 1, *, window_size: int = CORR_WINDOW_SIZE,
                  thresh_value: int = THRESH_VALUE, thresh_frac_bits: int = THRESH_FRAC_BITS,
                  min_corr_mag: float = MIN_CORR_MAG, hysteresis: int = HYSTERESIS, normalize: bool = True,
                  outputs=("gate_mask",), max_events: int = 8, device=None):
-        dev = torch.device(device) if device is not None else _lib.require_gpu()
-        lib = _lib.lib()
-        nbytes = int(lib.ofs_zc_chunk_state_bytes(int(window_size)))
-        if nbytes < 0 or B < 0 or n_branch < 1:
-            raise ValueError(f"ZCChunkedDetector: window_size 0 .. 65536, B >= 0, n_branch >= 1 "
-                             f"(got window_size={window_size}, B={B}, n_branch={n_branch})")
+        supports = (f"ZCChunkedDetector: window_size 0 .. 65536, B >= 0, n_branch >= 1 "
+                    f"(got window_size={window_size}, B={B}, n_branch={n_branch})")
+        if n_branch < 1:
+            raise ValueError(supports)
+        super().__init__(B, device, (int(window_size),), supports)
         names = [k for k, _ in CHUNK_ARRAYS]
         bad = [k for k in outputs if k not in names]
         if bad:
             raise ValueError(f"outputs must be among {names}, got {bad}")
         if reference is None:
             reference = build_pss_symbol(include_cp=False)
-        self.mf = reference if isinstance(reference, MatchedFilter) else MatchedFilter(reference, dev)
+        self.mf = reference if isinstance(reference, MatchedFilter) else MatchedFilter(reference, self.device)
         self.N = len(self.mf)
-        self.B, self.n_branch, self.device = int(B), int(n_branch), dev
+        self.n_branch = int(n_branch)
         self.mode = OFS_ZC_V2 if normalize else OFS_ZC_SUM
         self.outputs = tuple(outputs)
         if int(max_events) < 0:
@@ -470,37 +471,27 @@ class ZCChunkedDetector:
         self.max_events = int(max_events)          # 0: counts, mask and open_gate_start only (no event arrays)
         self._par = (int(window_size), int(thresh_value), int(thresh_frac_bits), float(min_corr_mag),
                      self.N, int(hysteresis))
-        self.state = torch.zeros((self.B, nbytes), dtype=torch.uint8, device=dev)      # all-zero = fresh
         self.history = None            # [B, n_branch, N - 1] samples, in the format of the first push
-        self._fn = lib.ofs_zc_detect_chunk
-        self._bufs: dict = {}
 
-    def _buffers(self, kind: str, Tc: int) -> ZCChunkResult:
-        """The cached result of (kind of call, Tc): the shape is part of the key, so a Tc = 0 flush and a
+    def _alloc(self, Tc: int) -> ZCChunkResult:
+        """One result per (kind of call, Tc): the kind is part of the cache key, so a Tc = 0 flush and a
         tail flush, or a push and a push_mag of one length, never share buffers."""
-        key = (kind, Tc)
-        r = self._bufs.get(key)
-        if r is None:
-            B, dev, E = self.B, self.device, max(self.max_events, 1)
-            arr = {k: (torch.zeros((B, Tc), dtype=dt, device=dev) if k in self.outputs and Tc else None)
-                   for k, dt in CHUNK_ARRAYS}
-            r = self._bufs[key] = ZCChunkResult(
-                **arr, n_events=torch.zeros((B,), dtype=torch.int32, device=dev),
-                events=torch.zeros((B, E, 4), dtype=torch.int64, device=dev),
-                peak_values=torch.zeros((B, E), dtype=torch.float64, device=dev),
-                open_gate_start=torch.full((B,), -1, dtype=torch.int64, device=dev))
-        return r
+        B, dev, E = self.B, self.device, max(self.max_events, 1)
+        arr = {k: (torch.zeros((B, Tc), dtype=dt, device=dev) if k in self.outputs and Tc else None)
+               for k, dt in CHUNK_ARRAYS}
+        return ZCChunkResult(
+            **arr, n_events=torch.zeros((B,), dtype=torch.int32, device=dev),
+            events=torch.zeros((B, E, 4), dtype=torch.int64, device=dev),
+            peak_values=torch.zeros((B, E), dtype=torch.float64, device=dev),
+            open_gate_start=torch.full((B,), -1, dtype=torch.int64, device=dev))
 
-    def _call(self, mag, ld: int, Tc: int, final: bool, kind: str) -> ZCChunkResult:
-        r = self._buffers(kind, Tc)
-        rc = self._fn(_lib.ptr(mag), int(ld), self.B, Tc, *self._par, self.state.data_ptr(),
-                      _lib.ptr(r.local_sum), _lib.ptr(r.corr_scaled), _lib.ptr(r.thresh_scaled),
-                      _lib.ptr(r.above_threshold), _lib.ptr(r.metric_valid), _lib.ptr(r.gate_mask),
-                      self.max_events, r.n_events.data_ptr(), r.events.data_ptr() if self.max_events else None,
-                      r.peak_values.data_ptr() if self.max_events else None,
-                      r.open_gate_start.data_ptr(), int(bool(final)), _lib.stream_ptr())
-        _lib.check(rc, "ofs_zc_detect_chunk")
-        return r
+    def _launch(self, mag, Tc: int, final: int, r: ZCChunkResult, ld: int):
+        return self._fn(mag, ld, self.B, Tc, *self._par, self.state.data_ptr(),
+                        _lib.ptr(r.local_sum), _lib.ptr(r.corr_scaled), _lib.ptr(r.thresh_scaled),
+                        _lib.ptr(r.above_threshold), _lib.ptr(r.metric_valid), _lib.ptr(r.gate_mask),
+                        self.max_events, r.n_events.data_ptr(), r.events.data_ptr() if self.max_events else None,
+                        r.peak_values.data_ptr() if self.max_events else None,
+                        r.open_gate_start.data_ptr(), final, _lib.stream_ptr())
 
     def push_mag(self, corr_mag: torch.Tensor, final: bool = False, _kind: str = "mag") -> ZCChunkResult:
         """The next ``Tc`` magnitudes ``[B, Tc]`` float64 of every stream in ONE ofs_zc_detect_chunk call.
@@ -516,7 +507,7 @@ class ZCChunkedDetector:
         if Tc > 1 and corr_mag.stride(1) != 1 or (self.B > 1 and corr_mag.stride(0) < Tc):
             corr_mag = corr_mag.contiguous()
         ld = corr_mag.stride(0) if self.B > 1 else max(Tc, 1)
-        return self._call(corr_mag if Tc and self.B else None, ld, Tc, final, _kind)
+        return self._call(corr_mag if Tc and self.B else None, Tc, final, _kind, ld=int(ld))
 
     def _samples(self, x):
         """x as a device tensor [B, n_branch, Tc] (+ a trailing I/Q axis for int16)."""
@@ -558,7 +549,7 @@ class ZCChunkedDetector:
         ``T + N - 1`` and emit; the streams are fresh afterwards (and may continue in another sample
         format).  Before any push there is no tail: the call only closes what ``push_mag`` left open."""
         if self.N == 1 or self.B == 0 or self.history is None:
-            r = self._call(None, 1, 0, True, "flush")
+            r = self._call(None, 0, True, "flush", ld=1)
         else:
             r = self._push(torch.zeros_like(self.history), True, "flush")
         self.history = None
@@ -567,14 +558,12 @@ class ZCChunkedDetector:
     def reset(self, mask: torch.Tensor | None = None) -> None:
         """Make all streams fresh, or those where ``mask`` [B] (bool) is set, without closing their
         gates (stream-ordered, no synchronisation)."""
+        super().reset(mask)
         if mask is None:
-            self.state.zero_()
             self.history = None
-        else:
+        elif self.history is not None:
             m = torch.as_tensor(mask, dtype=torch.bool).to(self.device)
-            self.state.masked_fill_(m[:, None], 0)
-            if self.history is not None:
-                self.history.masked_fill_(m.reshape((-1,) + (1,) * (self.history.dim() - 1)), 0)
+            self.history.masked_fill_(m.reshape((-1,) + (1,) * (self.history.dim() - 1)), 0)
 
 
 def detect_zc_preamble(rx_samples, window_size: int = CORR_WINDOW_SIZE, thresh_value: int = THRESH_VALUE,

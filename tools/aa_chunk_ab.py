@@ -26,16 +26,7 @@ import torch  # noqa: E402
 
 from ofdm_sync_amd import _lib, sync_aa, synth  # noqa: E402
 from bench_configs import int12  # noqa: E402
-
-
-def timed(fn, steps, st):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(st)
-    for _ in range(steps):
-        fn()
-    e1.record(st)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
+from chunk_ab_common import timed  # noqa: E402
 
 
 def main():

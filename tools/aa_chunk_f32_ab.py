@@ -28,20 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "ofdm-sync-math_amd"))
 import torch  # noqa: E402
 
 from ofdm_sync_amd import _lib, sync_aa, synth  # noqa: E402
-
-
-def timed(fn, steps, st):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(st)
-    for _ in range(steps):
-        fn()
-    e1.record(st)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
-
-
-def bits(t):
-    return (torch.view_as_real(t) if t.is_complex() else t).contiguous().view(torch.int32)
+from chunk_ab_common import bits, timed  # noqa: E402
 
 
 def main():

@@ -33,20 +33,11 @@ import torch  # noqa: E402
 
 from ofdm_sync_amd import _lib, minn_rtl, synth  # noqa: E402
 from bench_configs import int12  # noqa: E402
+from chunk_ab_common import timed  # noqa: E402
 
 KEYS = ("corr_total", "corr_positive", "smooth_metric", "energy_total", "corr_scaled", "energy_scaled",
         "metric_valid", "above_threshold")
 SHIFT, THR, FRAC, HYST, TOFF, MAX_EV = 3, 3276, 15, 2, 0, 16
-
-
-def timed(fn, steps, st):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(st)
-    for _ in range(steps):
-        fn()
-    e1.record(st)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
 
 
 class OneShot:

@@ -35,19 +35,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ofdm_sync_amd import _lib, zc_v2  # noqa: E402
+from chunk_ab_common import timed  # noqa: E402
 
 STATE = ("local_sum", "corr_scaled", "thresh_scaled", "above_threshold", "metric_valid")
 FRAC, MIN_MAG, REFLEN, MAX_EV = 15, 0.3, 2048, 64
-
-
-def timed(fn, steps, st):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(st)
-    for _ in range(steps):
-        fn()
-    e1.record(st)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
 
 
 def make_mag(B, Tc, dev):

@@ -36,23 +36,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ofdm_sync_amd import _lib, zc_freq  # noqa: E402
+from chunk_ab_common import bits, timed  # noqa: E402
 
 CONFIGS = (("complex128", torch.complex128, _lib.C128, _lib.FP64, torch.float64, 1),
            ("complex64", torch.complex64, _lib.C64, _lib.FP32, torch.float32, 2))
-
-
-def timed(fn, steps, st):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(st)
-    for _ in range(steps):
-        fn()
-    e1.record(st)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
 
 
 def main():
