@@ -527,6 +527,22 @@ int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, i
                        double* slope_out, double* sto_out, void* stream);
 
 /*
+ * ofs_rx_backend with a stream origin, for frames cut out of a longer stream (ofs_frame_capture_chunk):
+ * origin [B] int64 (device), origin[b] = the absolute stream index of x[b][.][0].  It enters the CFO
+ * tone's phase index alone - exp(-i 2 pi cfo (origin + n) / fs) at local sample n - so a slice
+ * x = stream[.., o : o + T] decoded with origin = o and starts shifted by -o gives, BIT FOR BIT, every
+ * output of ofs_rx_backend on the whole stream.  The CP correlation and the bounds 0 <= n < T do not
+ * depend on it.  origin == NULL is ofs_rx_backend (the same kernels).  Everything else as above.
+ */
+int32_t ofs_rx_backend_at(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
+                          int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
+                          const int64_t* data_start, const double* cfo_in, int32_t n_used,
+                          const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
+                          const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
+                          void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
+                          double* slope_out, double* sto_out, const int64_t* origin, void* stream);
+
+/*
  * Batched receive-stream synthesis (benchmark / test input): the channel +
  * impairment chain of channel.apply_channel (channel.py:80-98), core.apply_cfo
  * (core.py:123-138) and sync_aa.quantize_adc (sync_aa.py:263-291):
@@ -956,6 +972,67 @@ int32_t ofs_zc_detect_chunk(const double* corr_mag, int64_t ld_mag, int64_t B, i
                             uint8_t* above_threshold, uint8_t* metric_valid, uint8_t* gate_mask,
                             int32_t max_events, int32_t* n_events, int64_t* ev_int, double* ev_peak,
                             int64_t* open_gate_start, int32_t final, void* stream);
+
+/*
+ * Resumable frame capture for chunk-fed streams: the link between the chunked detectors, whose events
+ * arrive after the frame's samples have left, and ofs_rx_backend_at, which wants the frame resident.
+ *
+ * A stream is fed in consecutive chunks of Tc samples.  The state (caller-owned, on the device) keeps the
+ * last `history` samples of every branch in the input's own format and a queue of at most `max_pending`
+ * frame starts.  Each call takes trigger indices from device memory - typically the frame_start column
+ * of a detector's event buffer written by the same push, so no host round trip - and emits every frame
+ * [s, s + frame_len) whose last sample has arrived, across any chunking.  The library allocates nothing,
+ * reads no environment and keeps no global state.
+ *   in_fmt     OFS_C64, OFS_C128 or OFS_CI16.  Packed 12-bit words (OFS_CP12) are not supported: their
+ *              samples straddle bytes, so a frame at an arbitrary start is no byte copy.
+ *   x          [B][n_br][Tc] samples in in_fmt (this call's chunk); n_br >= 1, branches kept apart.
+ *   frame_len  F >= 1 samples per frame and branch.
+ *   history    H, F <= H <= 2^30 - 4: the samples before the current chunk that stay retrievable.
+ *   max_pending  Q in 1 .. 16: queued starts per stream, and frames one call can emit per stream.
+ *   offset     added to every trigger; negative values capture a lead-in.
+ *   trig, trig_ld, trig_stride, n_trig, trig_max   stream b has k = min(max(n_trig[b], 0), trig_max)
+ *              triggers, trigger j gives s = trig[b * trig_ld + j * trig_stride] + offset (int64 elements;
+ *              n_trig [B] int32).  n_trig == NULL: no triggers in this call.  With ev_int [B][E][4] of
+ *              ofs_aa_detect_chunk(_f32): trig = &ev_int[0][0][3], trig_ld = 4 * E, trig_stride = 4,
+ *              n_trig = n_events, trig_max = E.
+ *   state      [B][ofs_frame_capture_state_bytes(in_fmt, n_br, frame_len, history, max_pending)] bytes,
+ *              16-byte aligned, device memory.  The layout is opaque; ALL-ZERO BYTES ARE A FRESH STREAM,
+ *              so any subset of streams is reset with a memset of its rows (stream-ordered with the
+ *              calls); in_fmt, n_br, frame_len, history and max_pending must not change between the calls
+ *              of a stream, and the calls of a stream must be ordered.
+ *   frames     [B][Q][n_br][F] samples in in_fmt, aligned to one sample.
+ *   frame_start [B][Q] int64, n_frames [B] int32, dropped [B][3] int32.
+ * Per stream, with n0 samples before the call and n1 = n0 + Tc, in this order:
+ *   1. Triggers in index order: s < max(0, n0 - H) (the samples are gone, or the index is negative) counts
+ *      in dropped[b][0] (late); else, with Q starts pending, in dropped[b][1] (queue full); else s joins
+ *      the queue.  Lateness is decided by `history` alone, whatever the storage is rounded to.
+ *   2. Pending starts in queue order: if s + F <= n1 the frame leaves the queue into the next output
+ *      slot: frame_start[b][slot] = s and frames[b][slot][br][0:F] = the stream's samples [s, s + F) of
+ *      every branch, bit for bit.  (H >= F: a queued start is still retrievable when it completes.)
+ *   3. n_frames[b] = slots written; frame_start[b][slot] = -1 for the unused slots; the sample words of
+ *      unused slots are left untouched; dropped[b][0..2] are this call's counts.  All written by every call.
+ *   4. final != 0: starts still pending count in dropped[b][2] (cut by the stream's end) and the stream
+ *      is fresh after the call.
+ *   5. Otherwise the state takes the chunk's newest samples and n1.
+ * Overlapping frames, unsorted triggers and several frames per call follow from these rules.  s + offset
+ * must not overflow int64.
+ *   Tc         any length >= 1 (there is no upper limit); Tc = 0 with final != 0 is a flush (x unused).
+ * Calls are stream-ordered and never synchronise with the host (two kernels per call: the gather, then
+ * one small workgroup per stream that writes the history, the bookkeeping outputs and the state).
+ * OFS_EINVAL (before any launch): a format other than the three above, n_br < 1, frame_len < 1, history <
+ * frame_len or above the limit, max_pending outside 1 .. 16, trig_max < 0, a null trig with n_trig given
+ * and trig_max > 0, B < 0, Tc < 0, Tc = 0 without final, a null or misaligned state or a null output with
+ * B > 0, a null x with B * Tc > 0.  B = 0 is a valid no-op.  ofs_frame_capture_state_bytes returns the
+ * bytes of ONE stream's state (a multiple of 16), or OFS_EINVAL (< 0) for unsupported arguments.
+ */
+int64_t ofs_frame_capture_state_bytes(int32_t in_fmt, int32_t n_br, int32_t frame_len, int32_t history,
+                                      int32_t max_pending);
+int32_t ofs_frame_capture_chunk(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t Tc,
+                                int32_t frame_len, int32_t history, int32_t max_pending, int64_t offset,
+                                const int64_t* trig, int64_t trig_ld, int64_t trig_stride,
+                                const int32_t* n_trig, int32_t trig_max, void* state,
+                                void* frames, int64_t* frame_start, int32_t* n_frames, int32_t* dropped,
+                                int32_t final, void* stream);
 
 /* ---- detection post-processing (metric streams -> timing decisions) -------------------------
  * Metrics are [B][n] device arrays; `precision` names their element type (OFS_FP32 = float,

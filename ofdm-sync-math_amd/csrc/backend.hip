@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 #include "ofdmsync.h"
 #include "ofs_common.h"
 #include "be_math.h"
@@ -42,6 +43,16 @@ struct BeArgs {
     double* cfo_out; double2* h_out; double2* xa_out; double2* gain_out; double* evm_out; double* evm_db_out;
     double* slope_out; double* sto_out;
 };
+// ofs_rx_backend_at: origin[b] = absolute stream index of x[b][.][0], added to the CFO tone's phase index
+// and to nothing else.  A kernel argument type of its own: the kernels without an origin keep theirs.
+struct BeArgsAt : BeArgs { const int64_t* origin; };
+template <bool ORG> struct BeArgsOf { using T = BeArgs; };
+template <> struct BeArgsOf<true> { using T = BeArgsAt; };
+template <bool ORG>
+__device__ __forceinline__ int64_t be_origin(const typename BeArgsOf<ORG>::T& a, int64_t b) {
+    if constexpr (ORG) return a.origin[b];
+    else return 0;
+}
 
 template <int FMT>
 __device__ __forceinline__ double2 ld(const void* p, int64_t i) {
@@ -239,10 +250,10 @@ __device__ __forceinline__ int bitrev(int v, int bits) { return (int)(__brev((un
 // tone of a thread's samples n = tid + BW·m comes from one sincos at its first sample and a
 // rotation by exp(i·phase(BW)) per step (angle addition: <= N/BW steps, ~1e-15 relative)
 template <int FMT>
-__device__ void load_window(const BeArgs& a, int64_t b, int64_t s, double cfo, double2* buf, int LB) {
+__device__ void load_window(const BeArgs& a, int64_t b, int64_t s, int64_t n0, double cfo, double2* buf, int LB) {
     const double w0 = 2.0 * M_PI * (-cfo);
     double sn, cs, ss, cc;
-    sincos(w0 * (double)(s + (int64_t)threadIdx.x) / a.fs, &sn, &cs);   // core.apply_cfo's phase
+    sincos(w0 * (double)(n0 + (int64_t)threadIdx.x) / a.fs, &sn, &cs);   // core.apply_cfo's phase
     sincos(w0 * (double)BW / a.fs, &ss, &cc);
     double2 tone = make_double2(cs, sn);
     const double2 step = make_double2(cc, ss);
@@ -368,11 +379,11 @@ struct BeCp {
 
 // window (registers) -> rx_eff = mean_br(x · exp(-i 2 pi cfo n / fs)) bit-reversed into buf
 template <int FMT, int SPT, int NBT>
-__device__ __forceinline__ void place_window(const BeArgs& a, int64_t s, double cfo, const BeWindow<FMT, SPT, NBT>& win,
+__device__ __forceinline__ void place_window(const BeArgs& a, int64_t s, int64_t n0, double cfo, const BeWindow<FMT, SPT, NBT>& win,
                                              double2* buf, int LB) {
     const double w0 = 2.0 * M_PI * (-cfo);
     double sn, cs, ss, cc;
-    ofs_bemath::sincos_lean(w0 * (double)(s + (int64_t)be_tid()) / a.fs, &sn, &cs);   // core.apply_cfo's phase
+    ofs_bemath::sincos_lean(w0 * (double)(n0 + (int64_t)be_tid()) / a.fs, &sn, &cs);   // core.apply_cfo's phase
     ofs_bemath::sincos_lean(w0 * (double)BW / a.fs, &ss, &cc);
     double2 tone = make_double2(cs, sn);
     const double2 step = make_double2(cc, ss);
@@ -785,13 +796,13 @@ __device__ __forceinline__ double2 be_tone_step(const BeArgs& a, double cfo) {
     return make_double2(cc, ss);
 }
 template <int FMT, int SPT, int NBT>
-__device__ __forceinline__ void place_window_fft(const BeArgs& a, int64_t s, double cfo,
+__device__ __forceinline__ void place_window_fft(const BeArgs& a, int64_t s, int64_t n0, double cfo,
                                                  const BeWindow<FMT, SPT, NBT>& win, double2* buf,
                                                  const double2* twq, double2 step_in) {
     constexpr int N = SPT * BW, LS = Log2<SPT>::value;
     const double w0 = 2.0 * M_PI * (-cfo);
     double sn, cs;
-    ofs_bemath::sincos_lean(w0 * (double)(s + (int64_t)be_tid()) / a.fs, &sn, &cs);   // core.apply_cfo's phase
+    ofs_bemath::sincos_lean(w0 * (double)(n0 + (int64_t)be_tid()) / a.fs, &sn, &cs);   // core.apply_cfo's phase
     double2 tone = make_double2(cs, sn);
     const double2 step = OFS_BE_STEP1 ? step_in : be_tone_step(a, cfo);
     double2 v[SPT];
@@ -876,8 +887,8 @@ __device__ __forceinline__ void fft_rest(double2* buf, const double2* twq) {
 #endif
 
 // (N = 4096: 80 KB of LDS, 2 workgroups per CU whatever the registers - so their budget is 256)
-template <int FMT, int SPT, int NBT, int UPT>
-__global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS_BE_MINWG)) void rx_backend_fast_kernel(BeArgs a) {
+template <int FMT, int SPT, int NBT, int UPT, bool ORG = false>
+__global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS_BE_MINWG)) void rx_backend_fast_kernel(typename BeArgsOf<ORG>::T a) {
 #if OFS_BE_TIMING
     long long tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long tprev = __builtin_amdgcn_s_memtime();
@@ -959,6 +970,7 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
     // earlier LDS read behind it)
     if (!(L40 && OFS_BE_NOFRAMEBAR && OFS_BE_RED2)) lds_barrier();
     const int64_t ps = a.pilot_start[b], ds = a.data_start[b];
+    const int64_t org = be_origin<ORG>(a, b);                         // (no origin: 0, folded away)
     if (!PF) {                        // (CPFIRST: the CFO would wait for the CP samples alone - vmcnt
         if (OFS_BE_CPFIRST) {         // counts in order - with the pilot window's loads still in flight)
             cpx.issue(a, b, ps);
@@ -992,12 +1004,12 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
     // ---- pilot: FFT, used bins, LS estimate ----
     if constexpr (L40) lds_barrier();                                 // the CFO sums' slots are read
     if constexpr (R8) {
-        place_window_fft<FMT, SPT, NBT>(a, ps + a.cp, cfo, pwin, buf, twq, tstep);
+        place_window_fft<FMT, SPT, NBT>(a, ps + a.cp, org + ps + a.cp, cfo, pwin, buf, twq, tstep);
         if constexpr (DEARLY) dwin.issue(a, b, ds + a.cp);
         BE_T(1)
         fft_rest<SPT>(buf, twq);
     } else {
-        place_window<FMT, SPT, NBT>(a, ps + a.cp, cfo, pwin, buf, LB);
+        place_window<FMT, SPT, NBT>(a, ps + a.cp, org + ps + a.cp, cfo, pwin, buf, LB);
         BE_T(1)
         fft_lds_q(buf, twq, N, LB);
     }
@@ -1036,8 +1048,8 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
     {
         if constexpr (!DEARLY) dwin.issue(a, b, ds + a.cp);
         if constexpr (L40) lds_barrier();                             // the fit sums' slots are read
-        if constexpr (R8) place_window_fft<FMT, SPT, NBT>(a, ds + a.cp, cfo, dwin, buf, twq, tstep);
-        else place_window<FMT, SPT, NBT>(a, ds + a.cp, cfo, dwin, buf, LB);
+        if constexpr (R8) place_window_fft<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, twq, tstep);
+        else place_window<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, LB);
     }
     if (PF && b + gridDim.x < a.B) {                           // the next frame's pilot window and
         const int64_t bn = b + gridDim.x;                             // CP samples land during this frame's
@@ -1095,8 +1107,8 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
 #endif
 }
 
-template <int FMT>
-__global__ __launch_bounds__(BW) void rx_backend_kernel(BeArgs a) {
+template <int FMT, bool ORG = false>
+__global__ __launch_bounds__(BW) void rx_backend_kernel(typename BeArgsOf<ORG>::T a) {
     extern __shared__ __attribute__((aligned(16))) double2 bsm[];
     __shared__ double red[BW / 64];
     __shared__ double scan_tot[BW / 64];
@@ -1114,6 +1126,7 @@ __global__ __launch_bounds__(BW) void rx_backend_kernel(BeArgs a) {
     lds_barrier();
     // ---- CFO (core.py:179-196) or given ----
     const int64_t ps = a.pilot_start[b];
+    const int64_t org = be_origin<ORG>(a, b);
     double cfo;
     if (a.cfo_in) {
         cfo = a.cfo_in[b];
@@ -1137,7 +1150,7 @@ __global__ __launch_bounds__(BW) void rx_backend_kernel(BeArgs a) {
     const double2* pil = a.pilot + b * a.pilot_stride;
     const double2* dat = a.data + b * a.data_stride;
     // ---- pilot: FFT, used bins, LS estimate ----
-    load_window<FMT>(a, b, ps + a.cp, cfo, buf, LB);
+    load_window<FMT>(a, b, ps + a.cp, org + ps + a.cp, cfo, buf, LB);
     fft_lds(buf, tw, N, LB);
     for (int u = threadIdx.x; u < U; u += BW) {
         int k = a.bins[u] % N;
@@ -1156,7 +1169,7 @@ __global__ __launch_bounds__(BW) void rx_backend_kernel(BeArgs a) {
         if (a.sto_out) a.sto_out[b] = -slope * (double)N / (2.0 * M_PI);
     }
     // ---- data: FFT, equalise, complex-gain alignment, EVM ----
-    load_window<FMT>(a, b, a.data_start[b] + a.cp, cfo, buf, LB);
+    load_window<FMT>(a, b, a.data_start[b] + a.cp, org + a.data_start[b] + a.cp, cfo, buf, LB);
     fft_lds(buf, tw, N, LB);
     double gr = 0.0, gi = 0.0, gx = 0.0, rr = 0.0;
     for (int u = threadIdx.x; u < U; u += BW) {
@@ -1193,13 +1206,14 @@ __global__ __launch_bounds__(BW) void rx_backend_kernel(BeArgs a) {
 
 }  // namespace
 
-extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
-                                  int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
-                                  const int64_t* data_start, const double* cfo_in, int32_t n_used,
-                                  const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
-                                  const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
-                                  void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
-                                  double* slope_out, double* sto_out, void* stream) {
+// ofs_rx_backend (origin == nullptr: the kernels without an origin) and ofs_rx_backend_at
+static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
+                          int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
+                          const int64_t* data_start, const double* cfo_in, int32_t n_used,
+                          const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
+                          const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
+                          void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
+                          double* slope_out, double* sto_out, const int64_t* origin, void* stream) {
     if (!(in_fmt == OFS_C64 || in_fmt == OFS_C128 || in_fmt == OFS_CI16) || OFS_MISSING(x, B * T) || B < 0 || n_br < 1 ||
         T < 0 || n_fft < 2 || n_fft > BNMAX || (n_fft & (n_fft - 1)) || cp_len < 0 || n_used < 1 ||
         n_used > n_fft || OFS_MISSING(pilot_start, B) || OFS_MISSING(data_start, B) || !bins || !pilot_used || !data_used ||
@@ -1210,6 +1224,9 @@ extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int3
              static_cast<const double2*>(pilot_used), pilot_stride, static_cast<const double2*>(data_used),
              data_stride, cfo_out, static_cast<double2*>(h_out), static_cast<double2*>(xa_out),
              static_cast<double2*>(gain_out), evm_out, evm_db_out, slope_out, sto_out};
+    BeArgsAt at{};
+    static_cast<BeArgs&>(at) = a;
+    at.origin = origin;
     const size_t lds = (size_t)n_fft * 16 + (size_t)(n_fft / 2) * 16 + (size_t)n_used * 24;
     hipStream_t st = (hipStream_t)stream;
     auto launch = [&](auto kern) -> int32_t {
@@ -1223,7 +1240,8 @@ extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int3
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, BW, lds) != hipSuccess)
             return OFS_EHIP;
         const int64_t grid = std::min<int64_t>(B, (int64_t)cus * std::max(per, 1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, a);
+        if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, at);
+        else hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, a);
         return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
     };
     // variant BE_FAST=0: the generic kernel (A/B)
@@ -1243,17 +1261,21 @@ extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int3
                 hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, BW, lds_f) != hipSuccess)
                 return OFS_EHIP;
             const int64_t grid = std::min<int64_t>(B, (int64_t)cus * std::max(per, 1));
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, a);
+            if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, at);
+            else hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, a);
             return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
         };
+#define BE_FAST1(F, SPT, NBT, UPT)                                                                   \
+        return origin ? launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT, true>)                     \
+                      : launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT>);
 #define BE_FAST(F)                                                                                   \
         switch (n_fft / BW * 10 + n_br) {                                                            \
-            case 41: return launch_f(rx_backend_fast_kernel<F, 4, 1, 3>);                            \
-            case 42: return launch_f(rx_backend_fast_kernel<F, 4, 2, 3>);                            \
-            case 81: return launch_f(rx_backend_fast_kernel<F, 8, 1, 5>);                            \
-            case 82: return launch_f(rx_backend_fast_kernel<F, 8, 2, 5>);                            \
-            case 161: return launch_f(rx_backend_fast_kernel<F, 16, 1, 10>);                         \
-            case 162: return launch_f(rx_backend_fast_kernel<F, 16, 2, 10>);                         \
+            case 41: BE_FAST1(F, 4, 1, 3)                                                            \
+            case 42: BE_FAST1(F, 4, 2, 3)                                                            \
+            case 81: BE_FAST1(F, 8, 1, 5)                                                            \
+            case 82: BE_FAST1(F, 8, 2, 5)                                                            \
+            case 161: BE_FAST1(F, 16, 1, 10)                                                         \
+            case 162: BE_FAST1(F, 16, 2, 10)                                                         \
         }
         switch (in_fmt) {
             case OFS_C64: BE_FAST(OFS_C64) break;
@@ -1261,12 +1283,37 @@ extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int3
             default: BE_FAST(OFS_CI16) break;
         }
 #undef BE_FAST
+#undef BE_FAST1
     }
     switch (in_fmt) {
-        case OFS_C64: return launch(rx_backend_kernel<OFS_C64>);
-        case OFS_C128: return launch(rx_backend_kernel<OFS_C128>);
-        default: return launch(rx_backend_kernel<OFS_CI16>);
+        case OFS_C64: return origin ? launch(rx_backend_kernel<OFS_C64, true>) : launch(rx_backend_kernel<OFS_C64>);
+        case OFS_C128: return origin ? launch(rx_backend_kernel<OFS_C128, true>) : launch(rx_backend_kernel<OFS_C128>);
+        default: return origin ? launch(rx_backend_kernel<OFS_CI16, true>) : launch(rx_backend_kernel<OFS_CI16>);
     }
+}
+
+extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
+                                  int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
+                                  const int64_t* data_start, const double* cfo_in, int32_t n_used,
+                                  const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
+                                  const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
+                                  void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
+                                  double* slope_out, double* sto_out, void* stream) {
+    return rx_backend(in_fmt, x, B, n_br, T, n_fft, cp_len, fs_hz, pilot_start, data_start, cfo_in, n_used, bins,
+                      pilot_used, pilot_stride, data_used, data_stride, cfo_out, h_out, xa_out, gain_out, evm_out,
+                      evm_db_out, slope_out, sto_out, nullptr, stream);
+}
+
+extern "C" int32_t ofs_rx_backend_at(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
+                                     int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
+                                     const int64_t* data_start, const double* cfo_in, int32_t n_used,
+                                     const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
+                                     const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
+                                     void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
+                                     double* slope_out, double* sto_out, const int64_t* origin, void* stream) {
+    return rx_backend(in_fmt, x, B, n_br, T, n_fft, cp_len, fs_hz, pilot_start, data_start, cfo_in, n_used, bins,
+                      pilot_used, pilot_stride, data_used, data_stride, cfo_out, h_out, xa_out, gain_out, evm_out,
+                      evm_db_out, slope_out, sto_out, origin, stream);
 }
 
 // ------------------------------------------------------------------------------------------

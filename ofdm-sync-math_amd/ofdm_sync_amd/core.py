@@ -150,12 +150,16 @@ def centered_subcarrier_indices(width: int) -> np.ndarray:
 
 def receiver_backend_batched(x, pilot_start, data_start, pilot_used, data_used, *, n_fft: int = N_FFT,
                              cp_len: int = CYCLIC_PREFIX, fs_hz: float = SAMPLE_RATE_HZ, bins=None,
-                             cfo_hz=None) -> dict:
+                             cfo_hz=None, origin=None) -> dict:
     """Per frame of x[B, n_branch, T]: CP CFO estimate at the pilot (unless cfo_hz [B] is given),
     CFO removal + branch mean, pilot FFT -> LS channel estimate -> phase-slope timing, data
     FFT -> equalise -> complex-gain alignment -> EVM.  pilot_used / data_used: [n_used] (shared)
     or [B, n_used] known symbols.  Returns device tensors: cfo [B], h [B, n_used], xa [B, n_used],
-    gain [B] complex, evm, evm_db, slope, sto [B]."""
+    gain [B] complex, evm, evm_db, slope, sto [B].  ``origin`` ([B] int64, or one value for all): the
+    absolute stream index of ``x[b, :, 0]`` when x holds frames cut out of longer streams
+    (``capture.FrameCapture``); it enters the CFO tone's phase index alone (``ofs_rx_backend_at``), so a
+    slice decoded with its origin and starts relative to the slice equals, bit for bit, the same frame
+    decoded inside the whole stream."""
     batch = _lib.as_batch(x, batched=True)
     dev = batch.data.device
     k = centered_subcarrier_indices(NUM_ACTIVE_SUBCARRIERS) if bins is None else np.asarray(bins)
@@ -188,13 +192,16 @@ def receiver_backend_batched(x, pilot_start, data_start, pilot_used, data_used, 
                xa=torch.empty((B, U), dtype=torch.complex128, device=dev),
                gain=torch.empty((B,), dtype=torch.complex128, device=dev), evm=f64(), evm_db=f64(), slope=f64(),
                sto=f64())
-    rc = _lib.lib().ofs_rx_backend(batch.fmt, batch.data.data_ptr(), B, batch.nb, batch.T, int(n_fft), int(cp_len),
-                                   float(fs_hz), ps.data_ptr(), ds.data_ptr(), _lib.ptr(cin), U, kb.data_ptr(),
-                                   pil.data_ptr(), pst, dat.data_ptr(), dst, out["cfo"].data_ptr(),
-                                   out["h"].data_ptr(), out["xa"].data_ptr(), out["gain"].data_ptr(),
-                                   out["evm"].data_ptr(), out["evm_db"].data_ptr(), out["slope"].data_ptr(),
-                                   out["sto"].data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "ofs_rx_backend")
+    args = (batch.fmt, batch.data.data_ptr(), B, batch.nb, batch.T, int(n_fft), int(cp_len),
+            float(fs_hz), ps.data_ptr(), ds.data_ptr(), _lib.ptr(cin), U, kb.data_ptr(),
+            pil.data_ptr(), pst, dat.data_ptr(), dst, out["cfo"].data_ptr(),
+            out["h"].data_ptr(), out["xa"].data_ptr(), out["gain"].data_ptr(),
+            out["evm"].data_ptr(), out["evm_db"].data_ptr(), out["slope"].data_ptr(), out["sto"].data_ptr())
+    if origin is None:
+        _lib.check(_lib.lib().ofs_rx_backend(*args, _lib.stream_ptr()), "ofs_rx_backend")
+    else:
+        org = dev_i64(origin)
+        _lib.check(_lib.lib().ofs_rx_backend_at(*args, org.data_ptr(), _lib.stream_ptr()), "ofs_rx_backend_at")
     return out
 
 

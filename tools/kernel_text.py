@@ -39,6 +39,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("files", nargs="+")
     ap.add_argument("--match", default="", help="only kernels whose demangled name contains this")
+    ap.add_argument("--renumber", action="store_true",
+                    help="hash the text with the function number of local labels (.LBB<fn>_<n>, .Ltmp<n>) and the "
+                         "kernel's own symbol replaced: two builds whose kernels differ only in their place in the "
+                         "file or in their mangled name then hash alike")
     a = ap.parse_args()
     sha = lambda rows: hashlib.sha1("\n".join(rows).encode()).hexdigest()[:12]   # noqa: E731
     print("| kernel | instructions | text sha1 | .amdhsa_ sha1 | " + " | ".join(FIELDS) + " |")
@@ -52,6 +56,8 @@ def main():
                 continue
             d = dict(r.split(None, 1) for r in hsa[sym])
             n = sum(1 for r in rows if not r.endswith(":") and not r.startswith("."))
+            if a.renumber:
+                rows = [re.sub(r"\.LBB\d+_", ".LBB_", r).replace(sym, "@self") for r in rows]
             print(f"| `{name}` | {n} | {sha(rows)} | {sha(hsa[sym])} | " +
                   " | ".join(d[".amdhsa_" + f] for f in FIELDS) + " |")
 
