@@ -543,6 +543,24 @@ int32_t ofs_rx_backend_at(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
                           double* slope_out, double* sto_out, const int64_t* origin, void* stream);
 
 /*
+ * ofs_rx_backend_at with the number of frames read on the device: n_active points to ONE int32 in device
+ * memory (e.g. n_rows of ofs_frame_capture_compact, written by an earlier call on the same stream).  The
+ * frames b < min(B, max(*n_active, 0)) are decoded exactly as ofs_rx_backend_at decodes them; no output
+ * word of any other row is written.  B stays the capacity: it sizes the arrays, the argument checks and
+ * the launch (the host does not know the count); a workgroup beyond the count leaves at once.
+ * n_active == NULL is ofs_rx_backend_at (the same kernels).  n_active given with origin == NULL is
+ * OFS_EINVAL.  Everything else as above.
+ */
+int32_t ofs_rx_backend_counted(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
+                               int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
+                               const int64_t* data_start, const double* cfo_in, int32_t n_used,
+                               const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
+                               const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
+                               void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
+                               double* slope_out, double* sto_out, const int64_t* origin,
+                               const int32_t* n_active, void* stream);
+
+/*
  * Batched receive-stream synthesis (benchmark / test input): the channel +
  * impairment chain of channel.apply_channel (channel.py:80-98), core.apply_cfo
  * (core.py:123-138) and sync_aa.quantize_adc (sync_aa.py:263-291):
@@ -1033,6 +1051,37 @@ int32_t ofs_frame_capture_chunk(int32_t in_fmt, const void* x, int64_t B, int32_
                                 const int32_t* n_trig, int32_t trig_max, void* state,
                                 void* frames, int64_t* frame_start, int32_t* n_frames, int32_t* dropped,
                                 int32_t final, void* stream);
+
+/*
+ * ofs_frame_capture_chunk with the frames written densely and their number left in device memory, so that
+ * ofs_rx_backend_counted can decode them without the host ever seeing a count.  Formats, trigger
+ * arguments, rules 1, 2, 4 and 5, `final`, the OFS_EINVAL conditions, the state layout and
+ * ofs_frame_capture_state_bytes are those of the slot form: after the same pushes the state bytes of the
+ * two are equal, and one stream may alternate between them.  Only where frames are written differs:
+ *   cap         capacity in rows, 1 .. 2^31 - 1 (anything else: OFS_EINVAL).
+ *   frames      [cap][n_br][F] samples in in_fmt, aligned to one sample.
+ *   frame_start [cap] int64, frame_stream [cap] int32, row0 [B] int32, n_rows [2] int32,
+ *   n_frames    [B] int32, dropped [B][3] int32 (as above).
+ * n_frames[b] = the frames of stream b that left the queue in this call (rule 2); row0[b] = the exclusive
+ * prefix sum of n_frames over b (exact in 64 bits, stored clamped to 2^31 - 1).  The frame of stream b in
+ * slot j belongs to row r = row0[b] + j: rows are in (stream, slot) order.  r < cap: the samples are
+ * written to frames[r], frame_start[r] = s, frame_stream[r] = b.  r >= cap: the frame is LOST - it has
+ * left the queue and is not retried.  n_rows[0] = min(total, cap), n_rows[1] = max(total - cap, 0) (lost;
+ * clamped to 2^31 - 1).  Every call writes n_rows, row0, n_frames, dropped, and -1 into frame_start[r] and
+ * frame_stream[r] for n_rows[0] <= r < cap; the sample words of those rows are left untouched.
+ * A null output with B > 0 is OFS_EINVAL.  B = 0 is a valid no-op that still writes n_rows = {0, 0} and
+ * the -1 fill where those pointers are given.
+ * Four kernels per call, stream-ordered, no host synchronisation: a thread per stream counts its frames,
+ * one workgroup scans the counts (deterministic; no workgroup waits on another), then the slot form's
+ * gather and update with the row as destination.
+ */
+int32_t ofs_frame_capture_compact(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t Tc,
+                                  int32_t frame_len, int32_t history, int32_t max_pending, int64_t offset,
+                                  const int64_t* trig, int64_t trig_ld, int64_t trig_stride,
+                                  const int32_t* n_trig, int32_t trig_max, void* state, int64_t cap,
+                                  void* frames, int64_t* frame_start, int32_t* frame_stream, int32_t* row0,
+                                  int32_t* n_rows, int32_t* n_frames, int32_t* dropped, int32_t final,
+                                  void* stream);
 
 /* ---- detection post-processing (metric streams -> timing decisions) -------------------------
  * Metrics are [B][n] device arrays; `precision` names their element type (OFS_FP32 = float,

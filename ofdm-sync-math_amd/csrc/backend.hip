@@ -46,12 +46,25 @@ struct BeArgs {
 // ofs_rx_backend_at: origin[b] = absolute stream index of x[b][.][0], added to the CFO tone's phase index
 // and to nothing else.  A kernel argument type of its own: the kernels without an origin keep theirs.
 struct BeArgsAt : BeArgs { const int64_t* origin; };
-template <bool ORG> struct BeArgsOf { using T = BeArgs; };
-template <> struct BeArgsOf<true> { using T = BeArgsAt; };
+// ofs_rx_backend_counted: the origin kernels with the number of frames read from device memory
+struct BeArgsCnt : BeArgsAt { const int32_t* n_active; };
+template <bool ORG, bool CNT = false> struct BeArgsOf { using T = BeArgs; };
+template <> struct BeArgsOf<true, false> { using T = BeArgsAt; };
+template <> struct BeArgsOf<true, true> { using T = BeArgsCnt; };
 template <bool ORG>
 __device__ __forceinline__ int64_t be_origin(const typename BeArgsOf<ORG>::T& a, int64_t b) {
     if constexpr (ORG) return a.origin[b];
     else return 0;
+}
+// the frames a kernel decodes: B, or min(B, max(*n_active, 0)) (one uniform load per workgroup)
+template <bool CNT, class A>
+__device__ __forceinline__ int64_t be_frames(const A& a) {
+    if constexpr (CNT) {
+        const int64_t n = *a.n_active;
+        return n < 0 ? 0 : (n < a.B ? n : a.B);
+    } else {
+        return a.B;
+    }
 }
 
 template <int FMT>
@@ -887,8 +900,11 @@ __device__ __forceinline__ void fft_rest(double2* buf, const double2* twq) {
 #endif
 
 // (N = 4096: 80 KB of LDS, 2 workgroups per CU whatever the registers - so their budget is 256)
-template <int FMT, int SPT, int NBT, int UPT, bool ORG = false>
-__global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS_BE_MINWG)) void rx_backend_fast_kernel(typename BeArgsOf<ORG>::T a) {
+template <int FMT, int SPT, int NBT, int UPT, bool ORG = false, bool CNT = false>
+__global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS_BE_MINWG)) void rx_backend_fast_kernel(typename BeArgsOf<ORG, CNT>::T a) {
+    const int64_t nfr = be_frames<CNT>(a);    // frames to decode (not counted: a.B itself)
+    if constexpr (CNT)
+        if ((int64_t)blockIdx.x >= nfr) return;              // a workgroup beyond the count leaves at once
 #if OFS_BE_TIMING
     long long tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long tprev = __builtin_amdgcn_s_memtime();
@@ -960,11 +976,11 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
     // latency hides under the pilot FFT, LS and unwrap; 32 VGPRs held meanwhile) or just before use
     constexpr bool DEARLY = (OFS_BE_DEARLY == 1 || (OFS_BE_DEARLY == 2 && SPT >= 16)) && R8;
     BeWindow<FMT, SPT, NBT> dwin;
-    if (PF && blockIdx.x < a.B) {
+    if (PF && blockIdx.x < nfr) {
         pwin.issue(a, blockIdx.x, a.pilot_start[blockIdx.x] + a.cp);
         cpx.issue(a, blockIdx.x, a.pilot_start[blockIdx.x]);
     }
-    for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
+    for (int64_t b = blockIdx.x; b < nfr; b += gridDim.x) {
     // (L40 + OFS_BE_NOFRAMEBAR: no barrier here - the CFO block sums write the other slot set than the
     // previous frame's last sums, RED2, and the barrier before the pilot window's placement orders every
     // earlier LDS read behind it)
@@ -1051,7 +1067,7 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
         if constexpr (R8) place_window_fft<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, twq, tstep);
         else place_window<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, LB);
     }
-    if (PF && b + gridDim.x < a.B) {                           // the next frame's pilot window and
+    if (PF && b + gridDim.x < nfr) {                           // the next frame's pilot window and
         const int64_t bn = b + gridDim.x;                             // CP samples land during this frame's
         pwin.issue(a, bn, a.pilot_start[bn] + a.cp);                  // data FFT, EQ and EVM
         cpx.issue(a, bn, a.pilot_start[bn]);
@@ -1107,8 +1123,11 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
 #endif
 }
 
-template <int FMT, bool ORG = false>
-__global__ __launch_bounds__(BW) void rx_backend_kernel(typename BeArgsOf<ORG>::T a) {
+template <int FMT, bool ORG = false, bool CNT = false>
+__global__ __launch_bounds__(BW) void rx_backend_kernel(typename BeArgsOf<ORG, CNT>::T a) {
+    const int64_t nfr = be_frames<CNT>(a);
+    if constexpr (CNT)
+        if ((int64_t)blockIdx.x >= nfr) return;
     extern __shared__ __attribute__((aligned(16))) double2 bsm[];
     __shared__ double red[BW / 64];
     __shared__ double scan_tot[BW / 64];
@@ -1122,7 +1141,7 @@ __global__ __launch_bounds__(BW) void rx_backend_kernel(typename BeArgsOf<ORG>::
         sincospi(-2.0 * (double)j / (double)N, &sn, &cs);
         tw[j] = make_double2(cs, sn);
     }
-    for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {    // frames, grid-stride
+    for (int64_t b = blockIdx.x; b < nfr; b += gridDim.x) {    // frames, grid-stride
     lds_barrier();
     // ---- CFO (core.py:179-196) or given ----
     const int64_t ps = a.pilot_start[b];
@@ -1206,14 +1225,17 @@ __global__ __launch_bounds__(BW) void rx_backend_kernel(typename BeArgsOf<ORG>::
 
 }  // namespace
 
-// ofs_rx_backend (origin == nullptr: the kernels without an origin) and ofs_rx_backend_at
+// ofs_rx_backend (origin == nullptr: the kernels without an origin), ofs_rx_backend_at and
+// ofs_rx_backend_counted (n_active given: the origin kernels with the count flag)
 static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
                           int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
                           const int64_t* data_start, const double* cfo_in, int32_t n_used,
                           const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
                           const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
                           void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
-                          double* slope_out, double* sto_out, const int64_t* origin, void* stream) {
+                          double* slope_out, double* sto_out, const int64_t* origin, const int32_t* n_active,
+                          void* stream) {
+    if (n_active && !origin) return OFS_EINVAL;
     if (!(in_fmt == OFS_C64 || in_fmt == OFS_C128 || in_fmt == OFS_CI16) || OFS_MISSING(x, B * T) || B < 0 || n_br < 1 ||
         T < 0 || n_fft < 2 || n_fft > BNMAX || (n_fft & (n_fft - 1)) || cp_len < 0 || n_used < 1 ||
         n_used > n_fft || OFS_MISSING(pilot_start, B) || OFS_MISSING(data_start, B) || !bins || !pilot_used || !data_used ||
@@ -1227,6 +1249,9 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
     BeArgsAt at{};
     static_cast<BeArgs&>(at) = a;
     at.origin = origin;
+    BeArgsCnt ct{};
+    static_cast<BeArgsAt&>(ct) = at;
+    ct.n_active = n_active;
     const size_t lds = (size_t)n_fft * 16 + (size_t)(n_fft / 2) * 16 + (size_t)n_used * 24;
     hipStream_t st = (hipStream_t)stream;
     auto launch = [&](auto kern) -> int32_t {
@@ -1240,7 +1265,8 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, BW, lds) != hipSuccess)
             return OFS_EHIP;
         const int64_t grid = std::min<int64_t>(B, (int64_t)cus * std::max(per, 1));
-        if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, at);
+        if constexpr (std::is_invocable_v<decltype(kern), BeArgsCnt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, ct);
+        else if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, at);
         else hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds, st, a);
         return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
     };
@@ -1261,13 +1287,15 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
                 hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, BW, lds_f) != hipSuccess)
                 return OFS_EHIP;
             const int64_t grid = std::min<int64_t>(B, (int64_t)cus * std::max(per, 1));
-            if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, at);
+            if constexpr (std::is_invocable_v<decltype(kern), BeArgsCnt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, ct);
+            else if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, at);
             else hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, a);
             return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
         };
 #define BE_FAST1(F, SPT, NBT, UPT)                                                                   \
-        return origin ? launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT, true>)                     \
-                      : launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT>);
+        return n_active ? launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT, true, true>)             \
+               : origin ? launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT, true>)                   \
+                        : launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT>);
 #define BE_FAST(F)                                                                                   \
         switch (n_fft / BW * 10 + n_br) {                                                            \
             case 41: BE_FAST1(F, 4, 1, 3)                                                            \
@@ -1285,11 +1313,15 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
 #undef BE_FAST
 #undef BE_FAST1
     }
+#define BE_GENERIC(F)                                                                                \
+    return n_active ? launch(rx_backend_kernel<F, true, true>)                                       \
+           : origin ? launch(rx_backend_kernel<F, true>) : launch(rx_backend_kernel<F>);
     switch (in_fmt) {
-        case OFS_C64: return origin ? launch(rx_backend_kernel<OFS_C64, true>) : launch(rx_backend_kernel<OFS_C64>);
-        case OFS_C128: return origin ? launch(rx_backend_kernel<OFS_C128, true>) : launch(rx_backend_kernel<OFS_C128>);
-        default: return origin ? launch(rx_backend_kernel<OFS_CI16, true>) : launch(rx_backend_kernel<OFS_CI16>);
+        case OFS_C64: BE_GENERIC(OFS_C64)
+        case OFS_C128: BE_GENERIC(OFS_C128)
+        default: BE_GENERIC(OFS_CI16)
     }
+#undef BE_GENERIC
 }
 
 extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
@@ -1301,7 +1333,7 @@ extern "C" int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int3
                                   double* slope_out, double* sto_out, void* stream) {
     return rx_backend(in_fmt, x, B, n_br, T, n_fft, cp_len, fs_hz, pilot_start, data_start, cfo_in, n_used, bins,
                       pilot_used, pilot_stride, data_used, data_stride, cfo_out, h_out, xa_out, gain_out, evm_out,
-                      evm_db_out, slope_out, sto_out, nullptr, stream);
+                      evm_db_out, slope_out, sto_out, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t ofs_rx_backend_at(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
@@ -1313,7 +1345,20 @@ extern "C" int32_t ofs_rx_backend_at(int32_t in_fmt, const void* x, int64_t B, i
                                      double* slope_out, double* sto_out, const int64_t* origin, void* stream) {
     return rx_backend(in_fmt, x, B, n_br, T, n_fft, cp_len, fs_hz, pilot_start, data_start, cfo_in, n_used, bins,
                       pilot_used, pilot_stride, data_used, data_stride, cfo_out, h_out, xa_out, gain_out, evm_out,
-                      evm_db_out, slope_out, sto_out, origin, stream);
+                      evm_db_out, slope_out, sto_out, origin, nullptr, stream);
+}
+
+extern "C" int32_t ofs_rx_backend_counted(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
+                                          int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
+                                          const int64_t* data_start, const double* cfo_in, int32_t n_used,
+                                          const int32_t* bins, const void* pilot_used, int64_t pilot_stride,
+                                          const void* data_used, int64_t data_stride, double* cfo_out, void* h_out,
+                                          void* xa_out, void* gain_out, double* evm_out, double* evm_db_out,
+                                          double* slope_out, double* sto_out, const int64_t* origin,
+                                          const int32_t* n_active, void* stream) {
+    return rx_backend(in_fmt, x, B, n_br, T, n_fft, cp_len, fs_hz, pilot_start, data_start, cfo_in, n_used, bins,
+                      pilot_used, pilot_stride, data_used, data_stride, cfo_out, h_out, xa_out, gain_out, evm_out,
+                      evm_db_out, slope_out, sto_out, origin, n_active, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -107,6 +107,9 @@ def _declare(lib):
                                      P, c_int32, P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P]),
         "ofs_rx_backend_at": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, c_double, P, P,
                                         P, c_int32, P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P, P]),
+        "ofs_rx_backend_counted": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, c_double, P,
+                                             P, P, c_int32, P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P,
+                                             P, P]),
         "ofs_synth_batch": (c_int32, [P, c_int64, c_int32, c_int64, c_int64, c_int32, c_double, c_double, c_double,
                                       c_double, c_double, ctypes.c_uint64, c_int32, c_double, P, P, P]),
         "ofs_synth_frames": (c_int32, [P, c_int64, P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
@@ -176,6 +179,9 @@ def _declare(lib):
         "ofs_frame_capture_chunk": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
                                               c_int64, P, c_int64, c_int64, P, c_int32, P, P, P, P, P,
                                               c_int32, P]),
+        "ofs_frame_capture_compact": (c_int32, [c_int32, P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                                c_int64, P, c_int64, c_int64, P, c_int32, P, c_int64, P, P, P, P,
+                                                P, P, P, c_int32, P]),
         "ofs_debug_set_variant": (c_int32, [ctypes.c_char_p, c_int64]),
         "ofs_debug_get_variant": (c_int64, [ctypes.c_char_p]),
         "ofs_debug_reset_variants": (c_int32, []),

@@ -150,7 +150,7 @@ def centered_subcarrier_indices(width: int) -> np.ndarray:
 
 def receiver_backend_batched(x, pilot_start, data_start, pilot_used, data_used, *, n_fft: int = N_FFT,
                              cp_len: int = CYCLIC_PREFIX, fs_hz: float = SAMPLE_RATE_HZ, bins=None,
-                             cfo_hz=None, origin=None) -> dict:
+                             cfo_hz=None, origin=None, n_active=None, out=None) -> dict:
     """Per frame of x[B, n_branch, T]: CP CFO estimate at the pilot (unless cfo_hz [B] is given),
     CFO removal + branch mean, pilot FFT -> LS channel estimate -> phase-slope timing, data
     FFT -> equalise -> complex-gain alignment -> EVM.  pilot_used / data_used: [n_used] (shared)
@@ -159,11 +159,27 @@ def receiver_backend_batched(x, pilot_start, data_start, pilot_used, data_used, 
     absolute stream index of ``x[b, :, 0]`` when x holds frames cut out of longer streams
     (``capture.FrameCapture``); it enters the CFO tone's phase index alone (``ofs_rx_backend_at``), so a
     slice decoded with its origin and starts relative to the slice equals, bit for bit, the same frame
-    decoded inside the whole stream."""
+    decoded inside the whole stream.  ``n_active`` (needs ``origin``): a device int32 tensor with ONE
+    element, read by the kernel and never by the host (a view such as ``res.n_rows[:1]`` of
+    ``capture.FrameCapture.push_compact`` is taken in place); the frames ``b < min(B, max(n_active, 0))``
+    are decoded and no output word of any other row is written (``ofs_rx_backend_counted``).  ``out``: a
+    dict returned by an earlier call of the same shape, written again instead of allocating.  Device
+    tensors for ``bins`` (int32) and ``cfo_hz`` (float64) are used as they are."""
     batch = _lib.as_batch(x, batched=True)
     dev = batch.data.device
-    k = centered_subcarrier_indices(NUM_ACTIVE_SUBCARRIERS) if bins is None else np.asarray(bins)
-    U = int(k.size)
+    if isinstance(bins, torch.Tensor):
+        kb = bins.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        U = int(kb.numel())
+    else:
+        k = centered_subcarrier_indices(NUM_ACTIVE_SUBCARRIERS) if bins is None else np.asarray(bins)
+        U = int(k.size)
+        kb = torch.as_tensor(k.astype(np.int32)).to(dev)
+    if n_active is not None:
+        if origin is None:
+            raise ValueError("n_active needs origin (ofs_rx_backend_counted decodes frames cut out of streams)")
+        if (not isinstance(n_active, torch.Tensor) or n_active.dtype != torch.int32 or n_active.numel() != 1
+                or n_active.device != dev):
+            raise ValueError(f"n_active must be an int32 tensor with one element on {dev}")
 
     def dev_i64(v):
         t = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
@@ -184,14 +200,25 @@ def receiver_backend_batched(x, pilot_start, data_start, pilot_used, data_used, 
     ps, ds = dev_i64(pilot_start), dev_i64(data_start)
     pil, pst = dev_ref(pilot_used)
     dat, dst = dev_ref(data_used)
-    kb = torch.as_tensor(k.astype(np.int32)).to(dev)
-    cin = None if cfo_hz is None else torch.as_tensor(np.asarray(cfo_hz, np.float64)).to(dev).reshape(-1).contiguous()
+    if cfo_hz is None:
+        cin = None
+    elif isinstance(cfo_hz, torch.Tensor):
+        cin = cfo_hz.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    else:
+        cin = torch.as_tensor(np.asarray(cfo_hz, np.float64)).to(dev).reshape(-1).contiguous()
     B = batch.B
-    f64 = lambda: torch.empty((B,), dtype=torch.float64, device=dev)   # noqa: E731
-    out = dict(cfo=f64(), h=torch.empty((B, U), dtype=torch.complex128, device=dev),
-               xa=torch.empty((B, U), dtype=torch.complex128, device=dev),
-               gain=torch.empty((B,), dtype=torch.complex128, device=dev), evm=f64(), evm_db=f64(), slope=f64(),
-               sto=f64())
+    shapes = dict(cfo=((B,), torch.float64), h=((B, U), torch.complex128), xa=((B, U), torch.complex128),
+                  gain=((B,), torch.complex128), evm=((B,), torch.float64), evm_db=((B,), torch.float64),
+                  slope=((B,), torch.float64), sto=((B,), torch.float64))
+    if out is None:
+        out = {key: torch.empty(shape, dtype=dt, device=dev) for key, (shape, dt) in shapes.items()}
+    else:
+        for key, (shape, dt) in shapes.items():
+            t = out.get(key) if isinstance(out, dict) else None
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev
+                    or not t.is_contiguous()):
+                raise ValueError(f"out[{key!r}] must be a contiguous {dt} tensor {shape} on {dev} "
+                                 "(the dict of an earlier call of the same shape)")
     args = (batch.fmt, batch.data.data_ptr(), B, batch.nb, batch.T, int(n_fft), int(cp_len),
             float(fs_hz), ps.data_ptr(), ds.data_ptr(), _lib.ptr(cin), U, kb.data_ptr(),
             pil.data_ptr(), pst, dat.data_ptr(), dst, out["cfo"].data_ptr(),
@@ -199,9 +226,13 @@ def receiver_backend_batched(x, pilot_start, data_start, pilot_used, data_used, 
             out["evm"].data_ptr(), out["evm_db"].data_ptr(), out["slope"].data_ptr(), out["sto"].data_ptr())
     if origin is None:
         _lib.check(_lib.lib().ofs_rx_backend(*args, _lib.stream_ptr()), "ofs_rx_backend")
-    else:
+    elif n_active is None:
         org = dev_i64(origin)
         _lib.check(_lib.lib().ofs_rx_backend_at(*args, org.data_ptr(), _lib.stream_ptr()), "ofs_rx_backend_at")
+    else:
+        org = dev_i64(origin)
+        _lib.check(_lib.lib().ofs_rx_backend_counted(*args, org.data_ptr(), n_active.data_ptr(), _lib.stream_ptr()),
+                   "ofs_rx_backend_counted")
     return out
 
 
