@@ -517,6 +517,18 @@ int32_t ofs_cp_search(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, in
  *   (0 = one row shared by all frames);  n_fft a power of two <= 4096.
  * Outputs (device, nullable): cfo_out [B], h_out / xa_out c128 [B][n_used], gain_out c128 [B],
  * evm_out, evm_db_out, slope_out (rad/bin), sto_out (samples) [B] f64.
+ * At the stream's edges (pilot_start / data_start may be negative or reach past T, T may be
+ * shorter than n_fft; pinned by tests/backend_frames.py and tests/test_gpu_backend_exact.py):
+ *   zero-fill: a window sample whose index i lies outside [0, T) is (+0, +0) - as is any zero
+ *     sample, whatever the tone's signs (the branch sum starts from +0);
+ *   pair-drop: the CP pair (pilot_start + n, pilot_start + n_fft + n), n < cp_len, counts only if
+ *     both indices are in [0, T); with no pair left (cp_len = 0 included) cfo_out = -0.0;
+ *   a frame decodes exactly like the same frame inside the stream padded with zeros at both ends
+ *     (ofs_rx_backend_at with origin = -pad: bit for bit, apart from the sign of a zero cfo_out);
+ *   windows wholly outside the stream: the spectrum is (+0, +0) on every bin, so h_out = ±0 with
+ *     numpy's signs for 0 / (pilot + 1e-9) - its phases are 0, -0 or ±pi and slope_out / sto_out
+ *     are np.unwrap's and the fit's on those - and a zero data window gives xa_out = gain_out = 0,
+ *     evm_out = 1.  Every output stays finite.
  */
 int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
                        int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,
@@ -533,6 +545,8 @@ int32_t ofs_rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, i
  * x = stream[.., o : o + T] decoded with origin = o and starts shifted by -o gives, BIT FOR BIT, every
  * output of ofs_rx_backend on the whole stream.  The CP correlation and the bounds 0 <= n < T do not
  * depend on it.  origin == NULL is ofs_rx_backend (the same kernels).  Everything else as above.
+ * origin is not checked: any int64 is taken, negative values included (a stream padded in front of
+ * its first sample has origin = -pad), and the phase index origin + n is converted to double as it is.
  */
 int32_t ofs_rx_backend_at(int32_t in_fmt, const void* x, int64_t B, int32_t n_br, int64_t T,
                           int32_t n_fft, int32_t cp_len, double fs_hz, const int64_t* pilot_start,

@@ -95,16 +95,19 @@ __device__ __forceinline__ double2 cdiv(double2 a, double2 b) {
     // Branch-free: both of numpy's cases are one formula on swapped operands (the larger |b|
     // component p, the other q; a's components u, v in the same order), so a wave whose lanes
     // split between the cases runs ONE pair of fp64 divisions instead of both branches' pairs.
-    // Bit-identical: case 2's real part a.x·rat + a.y = u + v·rat (addition commutes exactly) and
-    // its imaginary part a.y·rat - a.x = -(v - u·rat) (x - y = -(y - x) exactly, then ·scl).
+    // Bit-identical: case 2's real part a.x·rat + a.y = u + v·rat (addition commutes exactly); the
+    // imaginary parts a.y - a.x·rat (case 1) and a.y·rat - a.x (case 2) are both vi + u·rs with
+    // vi = a.y or -a.x and rs = -rat or rat (x - y = x + (-y) and addition commutes, exactly and with
+    // numpy's sign of a zero difference; -(v - u·rat) would be -0 where numpy has +0: a zero spectrum
+    // over a pilot with |b.y| > |b.x| then gave a phase of +pi where numpy's is -pi).
     // b = 0: numpy's a.x / |b.x|, a.y / |b.y| = a·(+inf) (signed inf, or NaN for a 0 or NaN part).
     const bool c1 = br >= bi;
     const double p = c1 ? b.x : b.y, q = c1 ? b.y : b.x;
-    const double u = c1 ? a.x : a.y, v = c1 ? a.y : a.x;
-    const double rat = q / p, scl = 1.0 / (p + q * rat);
-    const double re = (u + v * rat) * scl, t = (v - u * rat) * scl;
+    const double u = c1 ? a.x : a.y, v = c1 ? a.y : a.x, vi = c1 ? a.y : -a.x;
+    const double rat = q / p, scl = 1.0 / (p + q * rat), rs = c1 ? -rat : rat;
+    const double re = (u + v * rat) * scl, im = (vi + u * rs) * scl;
     const bool zero = br == 0.0 && bi == 0.0;
-    return make_double2(zero ? a.x * __builtin_inf() : re, zero ? a.y * __builtin_inf() : (c1 ? t : -t));
+    return make_double2(zero ? a.x * __builtin_inf() : re, zero ? a.y * __builtin_inf() : im);
 #else
     if (br >= bi) {
         if (br == 0.0 && bi == 0.0) return make_double2(a.x / br, a.y / bi);
