@@ -30,10 +30,7 @@
 
 namespace {
 
-#ifndef OFS_BE_WG
-#define OFS_BE_WG 256
-#endif
-constexpr int BW = OFS_BE_WG;     // threads per frame workgroup
+constexpr int BW = 256;           // threads per frame workgroup
 constexpr int BNMAX = 4096;
 
 struct BeArgs {
@@ -85,13 +82,9 @@ __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
 }
 // a / b exactly as numpy divides complex128 (Smith's algorithm with the reciprocal scale
 // scl = 1 / (b.x + b.y * rat), no contraction): bit-identical to numpy on the same operands
-#ifndef OFS_BE_CDIV_SEL
-#define OFS_BE_CDIV_SEL 1          // 0: numpy's two branches as branches (A/B)
-#endif
 __device__ __forceinline__ double2 cdiv(double2 a, double2 b) {
 #pragma clang fp contract(off)
     const double br = fabs(b.x), bi = fabs(b.y);
-#if OFS_BE_CDIV_SEL
     // Branch-free: both of numpy's cases are one formula on swapped operands (the larger |b|
     // component p, the other q; a's components u, v in the same order), so a wave whose lanes
     // split between the cases runs ONE pair of fp64 divisions instead of both branches' pairs.
@@ -108,15 +101,6 @@ __device__ __forceinline__ double2 cdiv(double2 a, double2 b) {
     const double re = (u + v * rat) * scl, im = (vi + u * rs) * scl;
     const bool zero = br == 0.0 && bi == 0.0;
     return make_double2(zero ? a.x * __builtin_inf() : re, zero ? a.y * __builtin_inf() : im);
-#else
-    if (br >= bi) {
-        if (br == 0.0 && bi == 0.0) return make_double2(a.x / br, a.y / bi);
-        const double rat = b.y / b.x, scl = 1.0 / (b.x + b.y * rat);
-        return make_double2((a.x + a.y * rat) * scl, (a.y - a.x * rat) * scl);
-    }
-    const double rat = b.x / b.y, scl = 1.0 / (b.y + b.x * rat);
-    return make_double2((a.x * rat + a.y) * scl, (a.y * rat - a.x) * scl);
-#endif
 }
 
 // workgroup barrier ordering LDS only: every barrier here orders LDS traffic (the global inputs
@@ -158,6 +142,15 @@ __device__ __forceinline__ double np_mod(double a, double b) {
         m = copysign(0.0, b);
     }
     return m;
+}
+
+// np.unwrap's correction of one phase step dd with |dd| >= pi (numpy's mod and boundary rule): what the
+// step adds to every later phase.  Callers test !(fabs(dd) < M_PI) themselves and add nothing otherwise
+// (an unconditional += 0.0 would turn a running -0 into +0)
+__device__ __forceinline__ double unwrap_fix(double dd) {
+    double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
+    if (dm == -M_PI && dd > 0.0) dm = M_PI;
+    return dm - dd;
 }
 
 // N-point forward DFT of buf (bit-reversed in, natural order out) in LDS; tw[j] = exp(-2 pi i j / N).
@@ -210,11 +203,7 @@ __device__ double unwrap_slope(double* ph, const int32_t* bins, int U, double* r
         double local = 0.0;
         for (int u = max(u0, 1); u < u1; ++u) {
             const double dd = ph[u] - ph[u - 1];
-            if (!(fabs(dd) < M_PI)) {                        // numpy's correction only where |dd| >= pi
-                double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
-                if (dm == -M_PI && dd > 0.0) dm = M_PI;
-                local += dm - dd;
-            }
+            if (!(fabs(dd) < M_PI)) local += unwrap_fix(dd); // numpy's correction only where |dd| >= pi
         }
         // exclusive block scan of the per-thread totals
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -236,11 +225,7 @@ __device__ double unwrap_slope(double* ph, const int32_t* bins, int U, double* r
             const double raw = ph[u];
             if (u >= 1) {
                 const double dd = raw - prev_raw;
-                if (!(fabs(dd) < M_PI)) {
-                    double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
-                    if (dm == -M_PI && dd > 0.0) dm = M_PI;
-                    run += dm - dd;
-                }
+                if (!(fabs(dd) < M_PI)) run += unwrap_fix(dd);
             }
             prev_raw = raw;
             ph[u] = raw + run;
@@ -291,15 +276,10 @@ __device__ void load_window(const BeArgs& a, int64_t b, int64_t s, int64_t n0, d
 
 // the thread index, opaque to the compiler inside the fast kernel's frame loop: values derived from
 // it (addresses, masks, bin indices) are recomputed per frame instead of being hoisted out of the
-// loop and held in registers across it (OFS_BE_REMAT = 0: plain threadIdx.x, A/B)
-#ifndef OFS_BE_REMAT
-#define OFS_BE_REMAT 1
-#endif
+// loop and held in registers across it
 __device__ __forceinline__ int be_tid() {
     int t = threadIdx.x;
-#if OFS_BE_REMAT
     asm volatile("" : "+v"(t));
-#endif
     return t;
 }
 
@@ -307,26 +287,12 @@ __device__ __forceinline__ int be_tid() {
 // are not hoisted out of the fast kernel's frame loop into registers held across it
 __device__ __attribute__((noinline)) double be_log10(double x) { return log10(x); }
 
-// the fast kernel's per-bin outputs (h, xa), streamed past the caches (nothing here reads them back):
-// r05ax, bit-identical, 0.710 -> 0.702 ms (N 2048), 0.819 -> 0.815 (1024), 0.898 -> 0.890 (4096)
-#ifndef OFS_BE_NT
-#define OFS_BE_NT 1
-#endif
+// the fast kernel's per-bin outputs (h, xa), streamed past the caches (nothing here reads them back) as
+// one 16-byte store each: r05ax, bit-identical, 0.710 -> 0.702 ms (N 2048), 0.819 -> 0.815 (1024),
+// 0.898 -> 0.890 (4096)
 typedef double be_d2v __attribute__((ext_vector_type(2)));
-#ifndef OFS_BE_ST16
-#define OFS_BE_ST16 1              // 0: two 8-byte halves per complex output (A/B)
-#endif
 __device__ __forceinline__ void be_st(double2* p, double2 v) {
-#if OFS_BE_NT
-#if OFS_BE_ST16
-    __builtin_nontemporal_store(be_d2v{v.x, v.y}, reinterpret_cast<be_d2v*>(p));   // one 16-byte store
-#else
-    __builtin_nontemporal_store(v.x, &p->x);
-    __builtin_nontemporal_store(v.y, &p->y);
-#endif
-#else
-    *p = v;
-#endif
+    __builtin_nontemporal_store(be_d2v{v.x, v.y}, reinterpret_cast<be_d2v*>(p));
 }
 
 template <int FMT> struct BeRaw { using T = float2; };          // the input word kept in registers
@@ -393,36 +359,6 @@ struct BeCp {
     }
 };
 
-// window (registers) -> rx_eff = mean_br(x · exp(-i 2 pi cfo n / fs)) bit-reversed into buf
-template <int FMT, int SPT, int NBT>
-__device__ __forceinline__ void place_window(const BeArgs& a, int64_t s, int64_t n0, double cfo, const BeWindow<FMT, SPT, NBT>& win,
-                                             double2* buf, int LB) {
-    const double w0 = 2.0 * M_PI * (-cfo);
-    double sn, cs, ss, cc;
-    ofs_bemath::sincos_lean(w0 * (double)(n0 + (int64_t)be_tid()) / a.fs, &sn, &cs);   // core.apply_cfo's phase
-    ofs_bemath::sincos_lean(w0 * (double)BW / a.fs, &ss, &cc);
-    double2 tone = make_double2(cs, sn);
-    const double2 step = make_double2(cc, ss);
-    const int rb = bitrev(be_tid(), LB);
-#pragma unroll
-    for (int m = 0; m < SPT; ++m) {
-        const int n = be_tid() + BW * m;
-        const int64_t i = s + n;
-        double2 acc = make_double2(0.0, 0.0);
-        if (i >= 0 && i < a.T) {
-#pragma unroll
-            for (int r = 0; r < NBT; ++r) {
-                const double2 w = cmul(widen(win.v[r][m]), tone);
-                acc.x += w.x; acc.y += w.y;
-            }
-            acc.x /= (double)NBT; acc.y /= (double)NBT;                 // np.mean over branches
-        }
-        buf[rb + bitrev(BW * m, LB)] = acc;                           // bit sets of tid and BW·m disjoint
-        tone = cmul(tone, step);
-    }
-    lds_barrier();
-}
-
 // ---- fast path: N = SPT·BW, NBT branches, cp <= 2·BW, n_used <= UPT·BW (compile time) ---------
 // Against the generic kernel below (r03q/r03r: a frame waited ~40 % of its time on serialized
 // HBM round trips, and its 77 KB of LDS held the CU at 2 workgroups):
@@ -432,10 +368,15 @@ __device__ __forceinline__ void place_window(const BeArgs& a, int64_t s, int64_t
 //    bins u = t + BW·j in the LS, EQ and EVM loops alike, so only the phases (unwrap: cross-bin)
 //    go to LDS;
 //  * the twiddle table holds N/4 entries (w^{j+N/4} = -i·w^j);
+//  * the FFT's first log2(SPT) stages run in registers at window placement, the other 8 as radix-8,
+//    radix-8, radix-4 passes over the swizzled buffer (place_window_fft, fft_rest);
 // so a workgroup needs N·16 + N/4·16 bytes of LDS (40 KB at N = 2048, the phases and reduction
-// slots overlaying the sample buffer: OFS_BE_LDS40) and, with be_math.h's lean atan2 / sincos,
-// 128 VGPRs: 4 workgroups (16 waves) per CU.
+// slots overlaying the sample buffer) and, with be_math.h's lean atan2 / sincos, 128 VGPRs: 4
+// workgroups (16 waves) per CU.
 // variant BE_FAST=0 selects the generic kernel (A/B).
+// The build switches that chose all this in rounds 3-6 are folded to their measured defaults and
+// their other arms deleted (the LDS radix-4 path, the two-barrier fit, own LDS for phases and slots,
+// the next-frame prefetch ...): DESIGN.md §4.8c lists them with their measurements.
 #ifndef OFS_BE_TIMING
 #define OFS_BE_TIMING 0            // diagnostic builds: per-phase cycles (tools/be_phase.py)
 #endif
@@ -447,78 +388,22 @@ __device__ unsigned long long be_prof[12];
 #define BE_T(i)
 #endif
 
-__device__ __forceinline__ double2 twq_at(const double2* twq, int j, int Q) {
-    if (j < Q) return twq[j];
-    const double2 v = twq[j - Q];
-    return make_double2(v.y, -v.x);                          // w^{j} = -i·w^{j-N/4}
-}
-
-// fft_lds with the quarter twiddle table (same butterflies, same order)
-__device__ void fft_lds_q(double2* buf, const double2* twq, int N, int LB) {
-    const int Q = N / 4;
-    int len = 2;
-    if (LB & 1) {
-        for (int j = threadIdx.x; j < N / 2; j += BW) {
-            const double2 u = buf[2 * j], v = buf[2 * j + 1];
-            const double2 t = cmul(twq[0], v);
-            buf[2 * j] = make_double2(u.x + t.x, u.y + t.y);
-            buf[2 * j + 1] = make_double2(u.x - t.x, u.y - t.y);
-        }
-        lds_barrier();
-        len = 4;
-    }
-    for (; len <= N; len <<= 2) {
-        const int h = len >> 1;
-        const int s1 = N / len, s2 = N / (2 * len);
-        for (int j = threadIdx.x; j < N / 4; j += BW) {
-            const int g = j / h, k = j - g * h;
-            const int p = g * 4 * h + k;
-            const double2 a0 = buf[p], a1 = buf[p + h], a2 = buf[p + 2 * h], a3 = buf[p + 3 * h];
-            const double2 w1 = twq_at(twq, k * s1, Q);
-            const double2 t1 = cmul(w1, a1), t3 = cmul(w1, a3);
-            const double2 b0 = make_double2(a0.x + t1.x, a0.y + t1.y), b1 = make_double2(a0.x - t1.x, a0.y - t1.y);
-            const double2 b2 = make_double2(a2.x + t3.x, a2.y + t3.y), b3 = make_double2(a2.x - t3.x, a2.y - t3.y);
-            const double2 u = cmul(twq_at(twq, k * s2, Q), b2), v = cmul(twq_at(twq, (k + h) * s2, Q), b3);
-            buf[p] = make_double2(b0.x + u.x, b0.y + u.y);
-            buf[p + 2 * h] = make_double2(b0.x - u.x, b0.y - u.y);
-            buf[p + h] = make_double2(b1.x + v.x, b1.y + v.y);
-            buf[p + 3 * h] = make_double2(b1.x - v.x, b1.y - v.y);
-        }
-        lds_barrier();
-    }
-}
-
-#ifndef OFS_BE_RED2
-#define OFS_BE_RED2 1              // fast kernel: block sums alternate between two slot sets, one barrier each
-#endif
-#ifndef OFS_BE_ZSCAN
-#define OFS_BE_ZSCAN 1             // block sums by the zero-filled DPP ladder (0: predicated ladder, A/B)
-#endif
-// NV block-wide sums with one pair of barriers: DPP wave sums (inclusive scan, lane 63), then the
-// BW/64 wave totals through LDS; every thread gets the NV results.
+// NV block-wide sums with one barrier: DPP wave sums (inclusive scan, lane 63), then the BW/64 wave
+// totals through LDS; every thread gets the NV results.  The fast kernel hands consecutive calls
+// one of two slot sets in turn (rs()), so the previous call's barrier already orders that set's last
+// readers before this call's writes; SYNC adds a barrier in front of the writes where the slots
+// overlay LDS data that other waves may still read.
 template <int NV, bool SYNC = false>
 __device__ __forceinline__ void block_sums(double (&v)[NV], double* red) {
     const int lane = be_tid() & 63, w = be_tid() >> 6;
-#if OFS_BE_ZSCAN
     // zero-filled DPP ladder (no lane predicates; the same additions in the same order), the wave
     // total written by lane 63 itself (no readlane)
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = ofs::scan_add(v[i]);
-    if (!OFS_BE_RED2 || SYNC) lds_barrier();                 // red's previous readers are done (RED2:
-                                                             // alternating slots, the previous call's
-                                                             // barrier orders them; SYNC: the slots
-                                                             // overlay LDS data other waves may still read)
+    if (SYNC) lds_barrier();
     if (lane == 63)
 #pragma unroll
         for (int i = 0; i < NV; ++i) red[w * NV + i] = v[i];
-#else
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = ofs::readlane(ofs::wave_scan_add(v[i], lane), 63);
-    lds_barrier();                                           // red's previous readers are done
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[w * NV + i] = v[i];
-#endif
     lds_barrier();
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -531,67 +416,19 @@ __device__ __forceinline__ void block_sums(double (&v)[NV], double* red) {
 
 // estimate_timing_offset_from_phase_slope (core.py:443-469) on ph[0..U) = angle(h) in LDS, with the
 // frame-invariant bin statistics precomputed (kmean, Σ kz, Σ kz² + 1e-12; kz = k - kmean): np.unwrap
-// as in unwrap_slope, the fit's two sums Σ phi and Σ kz·phi accumulated while each thread rewrites its
-// run, one reduction; slope = (Σ kz·phi - mean(phi)·Σ kz) / (Σ kz² + 1e-12)  (= Σ kz·(phi - mean) / ...).
-__device__ double unwrap_slope_fast(const double* ph, const int32_t* bins, int U, double kmean, double skz, double den,
-                                    double* red, double* scan_tot) {
-    const int per = (U + BW - 1) / BW;
-    const int u0 = be_tid() * per, u1 = min(U, u0 + per);
-    double local = 0.0;
-    for (int u = max(u0, 1); u < u1; ++u) {
-        const double dd = ph[u] - ph[u - 1];
-        if (!(fabs(dd) < M_PI)) {
-            double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
-            if (dm == -M_PI && dd > 0.0) dm = M_PI;
-            local += dm - dd;
-        }
-    }
-    const int lane = be_tid() & 63, w = be_tid() >> 6;
-    const double incl = OFS_BE_ZSCAN ? ofs::scan_add(local) : ofs::wave_scan_add(local, lane);
-    if (lane == 63) scan_tot[w] = incl;
-    lds_barrier();
-    double run = incl - local;
-    for (int k = 0; k < w; ++k) run += scan_tot[k];
-    double prev_raw = u0 >= 1 && u0 < U ? ph[u0 - 1] : 0.0;
-    double sv[2] = {0.0, 0.0};                               // Σ phi, Σ kz·phi
-    for (int u = u0; u < u1; ++u) {
-        const double raw = ph[u];
-        if (u >= 1) {
-            const double dd = raw - prev_raw;
-            if (!(fabs(dd) < M_PI)) {
-                double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
-                if (dm == -M_PI && dd > 0.0) dm = M_PI;
-                run += dm - dd;
-            }
-        }
-        prev_raw = raw;
-        const double phi = raw + run;
-        sv[0] += phi;
-        sv[1] += ((double)bins[u] - kmean) * phi;
-    }
-    block_sums<2>(sv, red);
-    const double pmean = sv[0] / (double)U;
-    return (sv[1] - pmean * skz) / den;
-}
-
-// The same fit with ONE pass over each thread's run and ONE barrier: phi(u) = raw(u) + C_t + lrun(u),
+// per bin as in unwrap_slope, slope = (Σ kz·phi - mean(phi)·Σ kz) / (Σ kz² + 1e-12)  (= Σ kz·(phi -
+// mean) / ...), with ONE pass over each thread's run and ONE barrier: phi(u) = raw(u) + C_t + lrun(u),
 // C_t the exclusive prefix (over threads) of the thread totals of the unwrap corrections, lrun the
 // thread's own running corrections, so  Σ phi = Σ_t (A_t + C_t·n_t)  and  Σ kz·phi = Σ_t (D_t + C_t·K_t)
 // with A_t = Σ (raw + lrun), D_t = Σ kz·(raw + lrun), K_t = Σ kz, n_t = count over the thread's bins.
 // Within a wave C_t = c_t (DPP exclusive scan) + P_w (the earlier waves' totals): each wave publishes
-// (Σ A_t + c_t n_t, Σ D_t + c_t K_t, its correction total, Σ n_t, Σ K_t) and every thread combines the
-// BW/64 records in wave order.  The sums associate differently from unwrap_slope_fast (slope / STO may
-// differ in the last bits; the unwrap itself is the same np.unwrap per bin).  OFS_BE_UNWRAP1 = 0: the
-// two-barrier form (A/B).
-#ifndef OFS_BE_UNWRAP1
-#define OFS_BE_UNWRAP1 1
-#endif
-// OFS_BE_WTOT: the records' bin counts and Σ kz are frame-invariant, so each wave's totals are scanned
-// once per workgroup (be_wave_totals: the same scans of the same values, the same bits) and held as
+// (Σ A_t + c_t n_t, Σ D_t + c_t K_t, its correction total) and every thread combines the BW/64 records
+// in wave order.  The sums associate differently from a scan, a second pass and a block reduction (the
+// two-barrier form of round 3, DESIGN.md §4.8c: slope / STO differ from it and from unwrap_slope in the
+// last bits; the unwrap itself is the same np.unwrap per bin).
+// The records' bin counts Σ n_t and Σ K_t are frame-invariant, so each wave's totals are scanned once
+// per workgroup (be_wave_totals: the same scans of the same values, the same bits) and held as
 // wave-uniform scalars; per frame only the three frame-dependent totals are scanned and published
-#ifndef OFS_BE_WTOT
-#define OFS_BE_WTOT 1
-#endif
 struct BeWaveTot { double n[BW / 64], k[BW / 64]; };
 __device__ __forceinline__ double be_uniform(double v) {
     const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
@@ -623,22 +460,18 @@ __device__ BeWaveTot be_wave_totals(const int32_t* bins, int U, double kmean, do
     lds_barrier();
     return t;
 }
-// OFS_BE_UNRW: the run's loop unrolled to its compile-time bound (runs are <= UPT bins) with every
-// phase and bin index read up front; the same operations in the same order, bit-identical.  0: the
-// runtime loop; 1: unrolled; 2 (default): unrolled for runs of 8+ bins (N 4096, 2 workgroups per CU:
-// 0.8057 -> 0.8017 ms; at N 2048 / 1024 slower, 0.6407 -> 0.6478 / 0.7560 -> 0.7632, r06aq)
-#ifndef OFS_BE_UNRW
-#define OFS_BE_UNRW 2
-#endif
+// The run's loop (runs are <= MAXPER = UPT bins): for runs of 8+ bins unrolled to that compile-time
+// bound with every phase and bin index read up front, the same operations in the same order, bit-
+// identical (N 4096, 2 workgroups per CU: 0.8057 -> 0.8017 ms); a runtime loop below that (unrolled,
+// N 2048 / 1024 were slower: 0.6407 -> 0.6478 / 0.7560 -> 0.7632, r06aq)
 template <int MAXPER>
 __device__ double unwrap_slope_1b(const double* ph, const int32_t* bins, int U, double kmean, double skz, double den,
-                                  double* red, double* kslot, const BeWaveTot& wt) {
+                                  double* red, const BeWaveTot& wt) {
     const int per = (U + BW - 1) / BW;
     const int u0 = be_tid() * per, u1 = min(U, u0 + per);
     double lrun = 0.0, A = 0.0, D = 0.0, K = 0.0, cnt = 0.0;
     double prev_raw = u0 >= 1 && u0 < U ? ph[u0 - 1] : 0.0;
-    constexpr bool UNR = OFS_BE_UNRW == 1 || (OFS_BE_UNRW == 2 && MAXPER >= 8);
-    if constexpr (UNR) {
+    if constexpr (MAXPER >= 8) {
     double rv[MAXPER];
     int bv[MAXPER];
 #pragma unroll
@@ -654,11 +487,7 @@ __device__ double unwrap_slope_1b(const double* ph, const int32_t* bins, int U, 
         const double raw = rv[i];
         if (u >= 1) {
             const double dd = raw - prev_raw;
-            if (!(fabs(dd) < M_PI)) {
-                double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
-                if (dm == -M_PI && dd > 0.0) dm = M_PI;
-                lrun += dm - dd;
-            }
+            if (!(fabs(dd) < M_PI)) lrun += unwrap_fix(dd);
         }
         prev_raw = raw;
         const double p = raw + lrun, kz = (double)bv[i] - kmean;
@@ -672,11 +501,7 @@ __device__ double unwrap_slope_1b(const double* ph, const int32_t* bins, int U, 
         const double raw = ph[u];
         if (u >= 1) {
             const double dd = raw - prev_raw;
-            if (!(fabs(dd) < M_PI)) {
-                double dm = np_mod(dd + M_PI, 2.0 * M_PI) - M_PI;
-                if (dm == -M_PI && dd > 0.0) dm = M_PI;
-                lrun += dm - dd;
-            }
+            if (!(fabs(dd) < M_PI)) lrun += unwrap_fix(dd);
         }
         prev_raw = raw;
         const double p = raw + lrun, kz = (double)bins[u] - kmean;
@@ -688,49 +513,47 @@ __device__ double unwrap_slope_1b(const double* ph, const int32_t* bins, int U, 
     }
     const int lane = be_tid() & 63, w = be_tid() >> 6;
     const double c = ofs::scan_add(lrun) - lrun;            // exclusive wave prefix of the thread totals
-    constexpr int NV = OFS_BE_WTOT ? 3 : 5;
-    double v[5] = {A + c * cnt, D + c * K, lrun, cnt, K};
+    constexpr int NV = 3;
+    double v[NV] = {A + c * cnt, D + c * K, lrun};
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = ofs::scan_add(v[i]);  // lane 63: the wave's totals
     if (lane == 63) {
 #pragma unroll
-        for (int i = 0; i < (OFS_BE_WTOT ? 3 : 4); ++i) red[w * 4 + i] = v[i];
-        if (!OFS_BE_WTOT) kslot[w] = v[4];
+        for (int i = 0; i < NV; ++i) red[w * 4 + i] = v[i];   // (records of 4 doubles, the last unused)
     }
     lds_barrier();
     double sphi = 0.0, skzphi = 0.0, pw = 0.0;
 #pragma unroll
     for (int k = 0; k < BW / 64; ++k) {
-        sphi += red[k * 4 + 0] + pw * (OFS_BE_WTOT ? wt.n[k] : red[k * 4 + 3]);
-        skzphi += red[k * 4 + 1] + pw * (OFS_BE_WTOT ? wt.k[k] : kslot[k]);
+        sphi += red[k * 4 + 0] + pw * wt.n[k];
+        skzphi += red[k * 4 + 1] + pw * wt.k[k];
         pw += red[k * 4 + 2];
     }
     const double pmean = sphi / (double)U;
     return (skzphi - pmean * skz) / den;
 }
 
-#ifndef OFS_BE_MINWG
-#define OFS_BE_MINWG 4             // workgroups per CU the register budget is cut for (128 VGPRs, with
-                                   // the 40 KB LDS layout, OFS_BE_LDS40).  r05ab: with the lean atan2 /
-                                   // sincos (be_math.h) the kernel needs 133 VGPRs, so 3 fit (0.94 ->
-                                   // 0.82 ms); r05ad: 4 at 127 VGPRs (4 spilled), 0.826 -> 0.755 ms, bit-
-                                   // identical.  (Round 3, with ocml's: 2 beat 3, 1.21 vs 1.29 ms.)
-#endif
+// Workgroups per CU the fast kernel's register budget is cut for (__launch_bounds__).
+// N = 2048 (40 KB of LDS): 4, i.e. 128 VGPRs.  r05ab: with the lean atan2 / sincos (be_math.h) the
+// kernel needs 133 VGPRs, so 3 fit (0.94 -> 0.82 ms); r05ad: 4 at 127 VGPRs (4 spilled), 0.826 ->
+// 0.755 ms, bit-identical.  (Round 3, with ocml's: 2 beat 3, 1.21 vs 1.29 ms.)
+constexpr int BE_MINWG = 4;
+// N = 1024 (20 KB of LDS): 5 (96 VGPRs, 4 spilled) 0.823 vs 4: 0.877 ms, 6 (80 VGPRs): 0.827 (r05ak)
+constexpr int BE_MINWG4 = 5;
+// (N = 4096: 80 KB of LDS, 2 workgroups per CU whatever the registers - so their budget is 256)
+
 // LDS layout of the fast kernel's sample buffer and quarter twiddle table: both are stored with an
 // XOR swizzle of the element index, so the window placement, the radix-8/8/4 passes and their
 // twiddle reads are free of bank conflicts.  Identity layout: SQ_LDS_BANK_CONFLICT was 60 % of the
 // kernel's LDS cycles (r05w); tools/lds_banks.py models every access (SPT 8: 5056 -> 1728 LDS
 // cycles per FFT and workgroup, the conflict-free count).  Both swizzles are linear over XOR, so
 // swz(p | i·h) = swz(p) ^ swz(i·h) for disjoint bit sets: a per-thread base XOR a constant.
-#ifndef OFS_BE_SWZ
-#define OFS_BE_SWZ 1               // 0: identity layout (A/B)
-#endif
 template <int SPT>
 __device__ __forceinline__ constexpr int bsw(int e) {
     constexpr int LS = __builtin_ctz(SPT);
-    return OFS_BE_SWZ ? e ^ ((e >> (LS + 5)) & 7) ^ (((e >> (LS + 3)) & 3) << LS) : e;
+    return e ^ ((e >> (LS + 5)) & 7) ^ (((e >> (LS + 3)) & 3) << LS);
 }
-__device__ __forceinline__ constexpr int tsw(int j) { return OFS_BE_SWZ ? j ^ (((j >> 4) ^ (j >> 8)) & 15) : j; }
+__device__ __forceinline__ constexpr int tsw(int j) { return j ^ (((j >> 4) ^ (j >> 8)) & 15); }
 
 // w^j for 0 <= j < N/2 from the swizzled quarter table, given as the swizzled index of j mod N/4
 // and j's quadrant bit: w^{j} = -i·w^{j-N/4}
@@ -801,10 +624,7 @@ template <> struct Log2<1> { static constexpr int value = 0; };
 // h = 1 pass, so those stages (twiddles w^{q·N/(2s)}) need no LDS round trip; the remaining 8
 // stages run as radix-8, radix-8, radix-4 passes (fft_rest).
 // the tone's per-BW-samples step e^{i·w0·BW/fs}: the same for both windows of a frame, so computed once
-// per frame (OFS_BE_STEP1; 0: per window, A/B) - the same expression, the same bits
-#ifndef OFS_BE_STEP1
-#define OFS_BE_STEP1 1
-#endif
+// per frame and passed to both placements - the same expression, the same bits as per window
 __device__ __forceinline__ double2 be_tone_step(const BeArgs& a, double cfo) {
     const double w0 = 2.0 * M_PI * (-cfo);
     double ss, cc;
@@ -814,13 +634,12 @@ __device__ __forceinline__ double2 be_tone_step(const BeArgs& a, double cfo) {
 template <int FMT, int SPT, int NBT>
 __device__ __forceinline__ void place_window_fft(const BeArgs& a, int64_t s, int64_t n0, double cfo,
                                                  const BeWindow<FMT, SPT, NBT>& win, double2* buf,
-                                                 const double2* twq, double2 step_in) {
+                                                 const double2* twq, double2 step) {
     constexpr int N = SPT * BW, LS = Log2<SPT>::value;
     const double w0 = 2.0 * M_PI * (-cfo);
     double sn, cs;
     ofs_bemath::sincos_lean(w0 * (double)(n0 + (int64_t)be_tid()) / a.fs, &sn, &cs);   // core.apply_cfo's phase
     double2 tone = make_double2(cs, sn);
-    const double2 step = OFS_BE_STEP1 ? step_in : be_tone_step(a, cfo);
     double2 v[SPT];
 #pragma unroll
     for (int m = 0; m < SPT; ++m) {
@@ -850,61 +669,26 @@ __device__ __forceinline__ void place_window_fft(const BeArgs& a, int64_t s, int
                 v[i0 + q + sp] = make_double2(u.x - t.x, u.y - t.y);
             }
     }
+    static_assert(BW == 256, "the thread index is reversed over 8 bits");
     const int db = bsw<SPT>(bitrev(be_tid(), 8) * SPT);                  // bsw(i) = i for i < SPT
 #pragma unroll
     for (int i = 0; i < SPT; ++i) buf[db ^ i] = v[i];
     lds_barrier();
 }
 
-// OFS_BE_WSYNC: for SPT <= 8 the first pass hands over to the second wave-locally - pass 1 thread j
+// For SPT <= 8 the first pass hands over to the second wave-locally (WSYNC) - pass 1 thread j
 // writes the 8·SPT elements of group j / SPT, pass 2 thread j reads the 64·SPT elements of group
 // G = j / (8·SPT), which pass-1 threads [8·SPT·G, 8·SPT·(G + 1)) wrote: 64 (SPT 8) or 32 (SPT 4)
 // threads of j's own wave (SPT 16: 128 threads, two waves - barrier)
-#ifndef OFS_BE_WSYNC
-#define OFS_BE_WSYNC 1
-#endif
 template <int SPT>
 __device__ __forceinline__ void fft_rest(double2* buf, const double2* twq) {
-    fft_pass<8, SPT, OFS_BE_WSYNC && SPT <= 8>(buf, twq, SPT);
+    fft_pass<8, SPT, SPT <= 8>(buf, twq, SPT);
     fft_pass<8, SPT>(buf, twq, 8 * SPT);
     fft_pass<4, SPT>(buf, twq, 64 * SPT);
 }
 
-#ifndef OFS_BE_PF
-#define OFS_BE_PF 0                // 1: the next frame's pilot window / CP loads issued during this frame's
-                                   // data phase (round 3, 0.97 vs 1.00 ms at 2 workgroups per CU; at 3:
-                                   // 0.820 vs 0.823 ms with 8 VGPR spills, r05ab - off)
-#endif
-#ifndef OFS_BE_MINWG4
-#define OFS_BE_MINWG4 5            // N = 1024 (20 KB of LDS): 5 (96 VGPRs, 4 spilled) 0.823 vs 4: 0.877 ms,
-                                   // 6 (80 VGPRs): 0.827 (r05ak)
-#endif
-#ifndef OFS_BE_LDS40
-#define OFS_BE_LDS40 1             // phases and reduction slots inside the sample buffer (0: own LDS, A/B)
-#endif
-#ifndef OFS_BE_MIDSLOTS
-#define OFS_BE_MIDSLOTS 1          // reduction slots over the spectrum's unused Nyquist bins (below)
-#endif
-#ifndef OFS_BE_NOFRAMEBAR
-#define OFS_BE_NOFRAMEBAR 1        // no barrier at the top of the frame loop under L40 (below)
-#endif
-#ifndef OFS_BE_DEARLY
-#define OFS_BE_DEARLY 2            // data window loads early: 0 never, 1 always, 2 for SPT >= 16 (N 4096: 2 workgroups
-#endif                             // per CU, registers to spare; r06aj 0.825 -> 0.813 ms; N 2048 / 1024 slower)
-#ifndef OFS_BE_CPFIRST
-#define OFS_BE_CPFIRST 0           // 1: CP loads issued before the pilot window's (A/B, r05au: 0.712 vs 0.709 ms
-#endif                             // at N 2048, 0.831 vs 0.818 at 1024, 0.895 vs 0.898 at 4096 - off)
-#ifndef OFS_BE_R8MAX
-#define OFS_BE_R8MAX 16            // largest SPT on the register-staged radix-8 path (N = 4096: 1.049 -> 0.898 ms
-                                   // with 215 VGPRs at its 2 workgroups per CU, r05as; 8: the LDS radix-4 path)
-#endif
-#ifndef OFS_BE_R8
-#define OFS_BE_R8 1                // 0: place_window + fft_lds_q (A/B)
-#endif
-
-// (N = 4096: 80 KB of LDS, 2 workgroups per CU whatever the registers - so their budget is 256)
 template <int FMT, int SPT, int NBT, int UPT, bool ORG = false, bool CNT = false>
-__global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS_BE_MINWG)) void rx_backend_fast_kernel(typename BeArgsOf<ORG, CNT>::T a) {
+__global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? BE_MINWG4 : BE_MINWG)) void rx_backend_fast_kernel(typename BeArgsOf<ORG, CNT>::T a) {
     const int64_t nfr = be_frames<CNT>(a);    // frames to decode (not counted: a.B itself)
     if constexpr (CNT)
         if ((int64_t)blockIdx.x >= nfr) return;              // a workgroup beyond the count leaves at once
@@ -916,33 +700,24 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
     constexpr int N = SPT * BW;
     double2* buf = bsm;                       // N
     double2* twq = bsm + N;                   // N / 4
-#if OFS_BE_LDS40
     // LDS = the sample buffer and the twiddle table only (40 KB at N = 2048: 4 workgroups per CU):
     // the phases live in the buffer between the pilot's LS and the unwrap (the pilot spectrum is in
-    // registers by then), the reduction slots at its end; barriers before each window placement
-    // keep the placement's writes behind the last reads of those slots
-    // OFS_BE_MIDSLOTS: the slots at the Nyquist end of the spectrum, buffer entries N/2 .. N/2 + 17 (bins
-    // within [N/2, N/2 + 64) whatever the swizzle: it permutes bits below 6 only), which centered used-bin
-    // sets never reach (the fast path's n_used <= N·5/8): when no used bin lies there (checked once per
-    // workgroup) the EQ block sums need no barrier before their slot writes; 0: at the buffer's end (A/B)
+    // registers by then), the reduction slots inside it too; barriers before each window placement
+    // keep the placement's writes behind the last reads of those slots.
+    // The slots sit at the Nyquist end of the spectrum: two sets of 4·(BW/64) doubles, the buffer's doubles
+    // N .. N + 31 = its entries N/2 .. N/2 + 15 (bins within [N/2, N/2 + 64) whatever the swizzle: it
+    // permutes bits below 6 only), which centered used-bin sets never reach (the fast path's n_used <=
+    // N·5/8): when no used bin lies there (checked once per workgroup) the EQ block sums need no barrier
+    // before their slot writes
     double* ph = reinterpret_cast<double*>(buf);                       // n_used <= N (the slots start at N)
-    double* red = reinterpret_cast<double*>(buf) + (OFS_BE_MIDSLOTS ? N : 2 * N - 9 * (BW / 64));
-    double* scan_tot = red + 8 * (BW / 64);
-#else
-    __shared__ double red[8 * (BW / 64)];
-    __shared__ double scan_tot[BW / 64];
-    double* ph = reinterpret_cast<double*>(twq + N / 4);   // n_used: phase / unwrap
-#endif
-    constexpr bool L40 = OFS_BE_LDS40;
-    int rp = 0;                                               // block-sum slot set (RED2: alternating)
-    auto rs = [&]() -> double* { if (OFS_BE_RED2) rp ^= 1; return red + rp * 4 * (BW / 64); };
-    const int U = a.n_used, LB = 31 - __clz(N);
-    constexpr bool R8 = OFS_BE_R8 && SPT <= OFS_BE_R8MAX;  // (round 3, with ocml math: 16 samples per thread spilled)
-    constexpr bool PF = OFS_BE_PF && SPT <= 8 && sizeof(typename BeRaw<FMT>::T) <= 8;   // (complex128 too)
+    double* red = reinterpret_cast<double*>(buf) + N;
+    int rp = 0;                                               // block-sum slot set, alternating
+    auto rs = [&]() -> double* { rp ^= 1; return red + rp * 4 * (BW / 64); };
+    const int U = a.n_used;
     for (int j = threadIdx.x; j < N / 4; j += BW) {
         double sn, cs;
         sincospi(-2.0 * (double)j / (double)N, &sn, &cs);
-        twq[R8 ? tsw(j) : j] = make_double2(cs, sn);
+        twq[tsw(j)] = make_double2(cs, sn);
     }
     int kb[UPT];                              // this thread's used bins u = tid + BW·j, as X indices
     double bsum[2] = {0.0, 0.0};
@@ -951,14 +726,14 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
         const int u = threadIdx.x + BW * j;
         int k = u < U ? a.bins[u] % N : 0;
         k = k < 0 ? k + N : k;
-        kb[j] = R8 ? bsw<SPT>(k) : k;                                     // buffer slot of bin k
+        kb[j] = bsw<SPT>(k);                                              // buffer slot of bin k
         if (u < U) bsum[0] += (double)a.bins[u];
         if (u < U && k >= N / 2 && k < N / 2 + 64) bsum[1] = 1.0;        // a used bin under the mid slots
     }
     // the phase-slope fit's frame-invariant sums (np.mean(k), Σ kz, Σ kz² + 1e-12)
     block_sums<2>(bsum, rs());
     const double kmean = bsum[0] / (double)U;
-    const bool slots_clear = L40 && OFS_BE_MIDSLOTS && bsum[1] == 0.0;   // EQ sums without the extra barrier
+    const bool slots_clear = bsum[1] == 0.0;                             // EQ sums without the extra barrier
     double kst[2] = {0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < UPT; ++j) {
@@ -972,33 +747,22 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
     block_sums<2>(kst, rs());
     const double skz = kst[0], kden = kst[1] + 1e-12;
     // (the slots: the reduction slot set rs() would hand out next, free until the frame loop)
-    const BeWaveTot wtot = OFS_BE_WTOT ? be_wave_totals(a.bins, U, kmean, red + (rp ^ 1) * 4 * (BW / 64)) : BeWaveTot{};
+    const BeWaveTot wtot = be_wave_totals(a.bins, U, kmean, red + (rp ^ 1) * 4 * (BW / 64));
     BeWindow<FMT, SPT, NBT> pwin;
     BeCp<FMT, NBT> cpx;
     // the data window's loads: issued right after the pilot window is placed (DEARLY: their HBM
-    // latency hides under the pilot FFT, LS and unwrap; 32 VGPRs held meanwhile) or just before use
-    constexpr bool DEARLY = (OFS_BE_DEARLY == 1 || (OFS_BE_DEARLY == 2 && SPT >= 16)) && R8;
+    // latency hides under the pilot FFT, LS and unwrap; 32 VGPRs held meanwhile) or just before use.
+    // Early for SPT >= 16 (N 4096: 2 workgroups per CU, registers to spare; r06aj 0.825 -> 0.813 ms;
+    // N 2048 / 1024 slower)
+    constexpr bool DEARLY = SPT >= 16;
     BeWindow<FMT, SPT, NBT> dwin;
-    if (PF && blockIdx.x < nfr) {
-        pwin.issue(a, blockIdx.x, a.pilot_start[blockIdx.x] + a.cp);
-        cpx.issue(a, blockIdx.x, a.pilot_start[blockIdx.x]);
-    }
     for (int64_t b = blockIdx.x; b < nfr; b += gridDim.x) {
-    // (L40 + OFS_BE_NOFRAMEBAR: no barrier here - the CFO block sums write the other slot set than the
-    // previous frame's last sums, RED2, and the barrier before the pilot window's placement orders every
-    // earlier LDS read behind it)
-    if (!(L40 && OFS_BE_NOFRAMEBAR && OFS_BE_RED2)) lds_barrier();
+    // (no barrier here - the CFO block sums write the other slot set than the previous frame's last
+    // sums, and the barrier before the pilot window's placement orders every earlier LDS read behind it)
     const int64_t ps = a.pilot_start[b], ds = a.data_start[b];
     const int64_t org = be_origin<ORG>(a, b);                         // (no origin: 0, folded away)
-    if (!PF) {                        // (CPFIRST: the CFO would wait for the CP samples alone - vmcnt
-        if (OFS_BE_CPFIRST) {         // counts in order - with the pilot window's loads still in flight)
-            cpx.issue(a, b, ps);
-            pwin.issue(a, b, ps + a.cp);
-        } else {
-            pwin.issue(a, b, ps + a.cp);
-            cpx.issue(a, b, ps);
-        }
-    }
+    pwin.issue(a, b, ps + a.cp);      // (the window first: CP loads first were slower at N 2048 / 1024,
+    cpx.issue(a, b, ps);              // r05au, as was the next frame's prefetch, r05ab / r06aj)
     double cfo;
     if (a.cfo_in) {
         cfo = a.cfo_in[b];
@@ -1016,22 +780,16 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
         cfo = -ofs_bemath::atan2_lean(pp[1], pp[0]) * a.fs / (2.0 * M_PI * (double)N);
     }
     if (a.cfo_out && be_tid() == 0) a.cfo_out[b] = cfo;
-    const double2 tstep = OFS_BE_STEP1 && R8 ? be_tone_step(a, cfo) : make_double2(0.0, 0.0);
+    const double2 tstep = be_tone_step(a, cfo);
     const double2* pil = a.pilot + b * a.pilot_stride;
     const double2* dat = a.data + b * a.data_stride;
     BE_T(0)
     // ---- pilot: FFT, used bins, LS estimate ----
-    if constexpr (L40) lds_barrier();                                 // the CFO sums' slots are read
-    if constexpr (R8) {
-        place_window_fft<FMT, SPT, NBT>(a, ps + a.cp, org + ps + a.cp, cfo, pwin, buf, twq, tstep);
-        if constexpr (DEARLY) dwin.issue(a, b, ds + a.cp);
-        BE_T(1)
-        fft_rest<SPT>(buf, twq);
-    } else {
-        place_window<FMT, SPT, NBT>(a, ps + a.cp, org + ps + a.cp, cfo, pwin, buf, LB);
-        BE_T(1)
-        fft_lds_q(buf, twq, N, LB);
-    }
+    lds_barrier();                                                    // the CFO sums' slots are read
+    place_window_fft<FMT, SPT, NBT>(a, ps + a.cp, org + ps + a.cp, cfo, pwin, buf, twq, tstep);
+    if constexpr (DEARLY) dwin.issue(a, b, ds + a.cp);
+    BE_T(1)
+    fft_rest<SPT>(buf, twq);
     BE_T(2)
     double2 hx[UPT];                                                  // h, later xhat
 #pragma unroll
@@ -1042,42 +800,29 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
             const double2 p = pil[u];
             const double2 h = cdiv(buf[kb[j]], make_double2(p.x + 1e-9, p.y));   // y / (x + eps)
             hx[j] = h;
-            if constexpr (!L40) ph[u] = ofs_bemath::atan2_lean(h.y, h.x);
             if (a.h_out) be_st(&a.h_out[b * U + u], h);
         }
     }
-    if constexpr (L40) {                                              // ph overlays the pilot spectrum
-        lds_barrier();
+    lds_barrier();                                                    // ph overlays the pilot spectrum
 #pragma unroll
-        for (int j = 0; j < UPT; ++j) {
-            const int u = be_tid() + BW * j;
-            if (u < U) ph[u] = ofs_bemath::atan2_lean(hx[j].y, hx[j].x);
-        }
+    for (int j = 0; j < UPT; ++j) {
+        const int u = be_tid() + BW * j;
+        if (u < U) ph[u] = ofs_bemath::atan2_lean(hx[j].y, hx[j].x);
     }
     lds_barrier();
     BE_T(3)
-    const double slope = (OFS_BE_UNWRAP1 && OFS_BE_RED2) ? unwrap_slope_1b<UPT>(ph, a.bins, U, kmean, skz, kden, rs(), scan_tot, wtot)
-                                                         : unwrap_slope_fast(ph, a.bins, U, kmean, skz, kden, rs(), scan_tot);
+    const double slope = unwrap_slope_1b<UPT>(ph, a.bins, U, kmean, skz, kden, rs(), wtot);
     if (be_tid() == 0) {
         if (a.slope_out) a.slope_out[b] = slope;
         if (a.sto_out) a.sto_out[b] = -slope * (double)N / (2.0 * M_PI);
     }
     BE_T(4)
     // ---- data: FFT, equalise, complex-gain alignment, EVM ----
-    {
-        if constexpr (!DEARLY) dwin.issue(a, b, ds + a.cp);
-        if constexpr (L40) lds_barrier();                             // the fit sums' slots are read
-        if constexpr (R8) place_window_fft<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, twq, tstep);
-        else place_window<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, LB);
-    }
-    if (PF && b + gridDim.x < nfr) {                           // the next frame's pilot window and
-        const int64_t bn = b + gridDim.x;                             // CP samples land during this frame's
-        pwin.issue(a, bn, a.pilot_start[bn] + a.cp);                  // data FFT, EQ and EVM
-        cpx.issue(a, bn, a.pilot_start[bn]);
-    }
+    if constexpr (!DEARLY) dwin.issue(a, b, ds + a.cp);
+    lds_barrier();                                                    // the fit sums' slots are read
+    place_window_fft<FMT, SPT, NBT>(a, ds + a.cp, org + ds + a.cp, cfo, dwin, buf, twq, tstep);
     BE_T(5)
-    if constexpr (R8) fft_rest<SPT>(buf, twq);
-    else fft_lds_q(buf, twq, N, LB);
+    fft_rest<SPT>(buf, twq);
     BE_T(6)
     double gs[4] = {0.0, 0.0, 0.0, 0.0};                              // vdot(xhat, ref), |xhat|², |ref|²
 #pragma unroll
@@ -1095,7 +840,7 @@ __global__ __launch_bounds__(BW, SPT >= 16 ? 2 : (SPT <= 4 ? OFS_BE_MINWG4 : OFS
         }
     }
     if (slots_clear) block_sums<4, false>(gs, rs());                  // (slots over unused bins only)
-    else block_sums<4, L40>(gs, rs());                                // (L40: the slots overlay the data spectrum)
+    else block_sums<4, true>(gs, rs());                               // (the slots overlay the data spectrum)
     const double rr = gs[3];
     BE_T(7)
     const double2 g = cdiv(make_double2(gs[0], gs[1]), make_double2(gs[2] + 1e-12, 0.0));
@@ -1255,9 +1000,8 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
     BeArgsCnt ct{};
     static_cast<BeArgsAt&>(ct) = at;
     ct.n_active = n_active;
-    const size_t lds = (size_t)n_fft * 16 + (size_t)(n_fft / 2) * 16 + (size_t)n_used * 24;
     hipStream_t st = (hipStream_t)stream;
-    auto launch = [&](auto kern) -> int32_t {
+    auto launch = [&](auto kern, size_t lds) -> int32_t {
         if (lds > 64 * 1024 &&
             hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return OFS_EHIP;
@@ -1278,27 +1022,12 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
                       ((n_fft == 4 * BW && n_used <= 3 * BW) || (n_fft == 8 * BW && n_used <= 5 * BW) ||
                        (n_fft == 16 * BW && n_used <= 10 * BW));
     if (fast) {
-        const size_t lds_f = (size_t)n_fft * 16 + (size_t)(n_fft / 4) * 16 + (OFS_BE_LDS40 ? 0 : (size_t)n_used * 8) +
-                             ofs::occ_lds();                       // variant OCC_LDS: occupancy A/B only
-        auto launch_f = [&](auto kern) -> int32_t {
-            if (lds_f > 64 * 1024 &&
-                hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess)
-                return OFS_EHIP;
-            int dev = 0, cus = 256, per = 1;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, BW, lds_f) != hipSuccess)
-                return OFS_EHIP;
-            const int64_t grid = std::min<int64_t>(B, (int64_t)cus * std::max(per, 1));
-            if constexpr (std::is_invocable_v<decltype(kern), BeArgsCnt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, ct);
-            else if constexpr (std::is_invocable_v<decltype(kern), BeArgsAt>) hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, at);
-            else hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BW), lds_f, st, a);
-            return hipGetLastError() == hipSuccess ? OFS_OK : OFS_EHIP;
-        };
+        // the sample buffer and the quarter twiddle table (variant OCC_LDS: occupancy A/B only)
+        const size_t lds_f = (size_t)n_fft * 16 + (size_t)(n_fft / 4) * 16 + ofs::occ_lds();
 #define BE_FAST1(F, SPT, NBT, UPT)                                                                   \
-        return n_active ? launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT, true, true>)             \
-               : origin ? launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT, true>)                   \
-                        : launch_f(rx_backend_fast_kernel<F, SPT, NBT, UPT>);
+        return n_active ? launch(rx_backend_fast_kernel<F, SPT, NBT, UPT, true, true>, lds_f)        \
+               : origin ? launch(rx_backend_fast_kernel<F, SPT, NBT, UPT, true>, lds_f)              \
+                        : launch(rx_backend_fast_kernel<F, SPT, NBT, UPT>, lds_f);
 #define BE_FAST(F)                                                                                   \
         switch (n_fft / BW * 10 + n_br) {                                                            \
             case 41: BE_FAST1(F, 4, 1, 3)                                                            \
@@ -1316,9 +1045,11 @@ static int32_t rx_backend(int32_t in_fmt, const void* x, int64_t B, int32_t n_br
 #undef BE_FAST
 #undef BE_FAST1
     }
+    // the generic kernel: the sample buffer, the half twiddle table, h / xhat and the phases
+    const size_t lds = (size_t)n_fft * 16 + (size_t)(n_fft / 2) * 16 + (size_t)n_used * 24;
 #define BE_GENERIC(F)                                                                                \
-    return n_active ? launch(rx_backend_kernel<F, true, true>)                                       \
-           : origin ? launch(rx_backend_kernel<F, true>) : launch(rx_backend_kernel<F>);
+    return n_active ? launch(rx_backend_kernel<F, true, true>, lds)                                  \
+           : origin ? launch(rx_backend_kernel<F, true>, lds) : launch(rx_backend_kernel<F>, lds);
     switch (in_fmt) {
         case OFS_C64: BE_GENERIC(OFS_C64)
         case OFS_C128: BE_GENERIC(OFS_C128)

@@ -2,7 +2,7 @@
 
 NumPy and the CPU oracle's conventions only; no GPU code.  model() restates ofdm_oracle.rx_backend with the rules
 at the stream's edges written out - the oracle cannot express them, because a negative numpy slice start wraps
-around.  Both kernels agree on these rules (load_window / place_window / place_window_fft, BeWindow::issue,
+around.  Both kernels agree on these rules (load_window / place_window_fft, BeWindow::issue,
 BeCp::issue and the generic kernel's CP loop):
 
   * zero-fill: a window sample whose stream index i lies outside [0, T) is +0.  The branch sum starts from

@@ -16,10 +16,10 @@ Which code each family reaches:
   delay  the unwrap's runs of ceil(U / 256) bins per thread, their stitching across threads and waves
          (unwrap_slope_1b with be_wave_totals; unwrap_slope), idle trailing threads, a 2 pi wrap on every run
          and wave boundary as d sweeps the odd delays; bin sets with k = 0, descending, beyond ±N/2, and under
-         the fast kernel's mid-buffer reduction slots (slots_clear == false: block_sums<4, L40>); fft_lds's lone
+         the fast kernel's mid-buffer reduction slots (slots_clear == false: block_sums<4, true>); fft_lds's lone
          radix-2 stage (n_fft 2, 8) and its absence (4); cp_len 0; n_used = n_fft.
   tie    np.unwrap's boundary rule (dm == -pi && dd > 0) on steps of exactly ±pi.
-  edge   BeWindow::issue's guarded arm, BeCp::issue's !full arm, the zero-fill of load_window, place_window and
+  edge   BeWindow::issue's guarded arm, BeCp::issue's !full arm, the zero-fill of load_window and
          place_window_fft, the CP correlation's per-pair guard in both kernels, T < n_fft, frames wholly outside
          the stream.  Each cut frame is also decoded inside the zero-padded stream at origin -P: negative origins
          reach be_origin unchecked (ofs_rx_backend_at takes any int64), and enter the tone's phase index alone.

@@ -2,8 +2,8 @@
 occupancy against the oracle, every frame.
 
 The fast kernel (csrc/backend.hip rx_backend_fast_kernel) overlays the unwrap phases and the
-block-sum reduction slots on its sample buffer (OFS_BE_LDS40) and alternates two slot sets with
-one barrier per reduction (OFS_BE_RED2).  A cross-wave ordering slip in that overlay only shows
+block-sum reduction slots on its sample buffer (the 40 KB overlay) and hands each block sum
+one of two slot sets in turn, one barrier per reduction (the alternating slot sets).  A cross-wave ordering slip in that overlay only shows
 when waves of different workgroups drift, i.e. with many more frames than resident workgroups,
 each workgroup looping over several frames.  So: 4096 frames x 2 branches (4-5 workgroups per
 CU x 256 CUs = 1024-1280 resident, 3-4 frames per workgroup), the largest used-bin count the
