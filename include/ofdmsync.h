@@ -719,6 +719,15 @@ int32_t ofs_zc_correlate(int32_t in_fmt, const void* x, int64_t B, int32_t n_br,
  * for one reference (host c128, N taps) and one batch shape; `scratch` must hold *scratch_bytes (the [rows * blocks][M] c128
  * spectra), `work` *work_bytes (rocFFT work area, may be 0).  A plan carries its rocFFT execution
  * state: use it from one host thread / stream at a time (one plan per concurrent caller).
+ *
+ * Non-finite samples.  ofs_zc_correlate gives a non-finite output exactly where the N-sample window
+ * holds a NaN or infinite sample, as the reference does.  Here a non-finite sample spoils its whole
+ * block: every output of each block whose M-sample input span [q*S - (N-1), q*S - (N-1) + M) holds
+ * it (S = M - N + 1; up to two blocks) may be NaN, which it is not in the reference.  Every output of
+ * every other block and of every other stream is what it is without that sample, bit for bit.
+ * Finite samples of any size: |corr| stays finite wherever corr does (|c| up to the fp64 range), and a
+ * window whose energy overflows to +inf gives 0 (corr / inf, zc_v2.py:269-271); once a block's energy
+ * prefix has overflowed, its later windows are summed directly.
  */
 int32_t ofs_zc_mf_plan_create(const void* ref, int32_t N, int64_t B, int32_t n_br, int64_t T, int32_t M,
                               void** plan_out, size_t* work_bytes, size_t* scratch_bytes);

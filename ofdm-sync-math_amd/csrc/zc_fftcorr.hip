@@ -64,6 +64,30 @@ struct McArgs {
     double ref_norm; double2* U; const double2* H; double2* out; double* mag;
 };
 
+constexpr double MC_DBL_MAX = 0x1.fffffffffffffp+1023;
+
+// Window energy where the block's prefix cannot give it: once a prefix has overflowed to +inf (or holds
+// a NaN) every later difference P[hi] - P[lo] is inf - inf, whatever the window holds.  Such an output
+// (finite data never has one) sums its N samples directly, as np.convolve(|x|^2, ones(N)) does
+// (zc_v2.py:266-268): +inf for a window that overflows, so the output is 0 as in the reference.
+template <int FMT>
+__device__ double mc_window_energy(const void* x, int64_t row, int64_t T, int64_t n, int N) {
+    double e = 0.0;
+    for (int64_t g = n - N + 1 > 0 ? n - N + 1 : 0; g <= n && g < T; ++g) {
+        const double2 v = ldx<FMT>(x, row * T + g);
+        e = fma(v.x, v.x, fma(v.y, v.y, e));
+    }
+    return e;
+}
+__device__ __forceinline__ bool mc_finite(double v) { return v <= MC_DBL_MAX && v >= -MC_DBL_MAX; }
+// |c| of the one-block kernel: sqrt(re^2 + im^2), or hypot where the sum of squares overflows or is NaN
+// (|c| > 1.3e154; numpy's hypot stays finite there); every finite word as before
+__device__ __forceinline__ double mf_cabs(double2 c) {
+    const double s = fma(c.x, c.x, c.y * c.y);
+    if (!(s <= MC_DBL_MAX)) return hypot(c.x, c.y);
+    return sqrt(s);
+}
+
 // U[(row·nblk + q)][m] = xz_row[q·S - (N-1) + m]
 template <int FMT>
 __global__ __launch_bounds__(FW) void mc_pack_kernel(McArgs a) {
@@ -439,16 +463,18 @@ __global__ __launch_bounds__(MF_T) void mc_fused_kernel(McArgs a, const double2*
         // row), without hypot's scaling branches and two fp64 divisions per output
         if (a.mode == OFS_ZC_RAW || a.mode == OFS_ZC_SUM) {
             if (a.out) a.out[oi] = c;
-            if (a.mag) a.mag[oi] = sqrt(fma(c.x, c.x, c.y * c.y));
+            if (a.mag) a.mag[oi] = mf_cabs(c);
             continue;
         }
-        const double e = P[mf_pq(o + 1)] - P[mf_pq(o + 1 - a.N)];  // Σ |x|^2 over the N-sample window
+        const double phi = P[mf_pq(o + 1)];
+        double e = phi - P[mf_pq(o + 1 - a.N)];                    // Σ |x|^2 over the N-sample window
+        if (!mc_finite(phi)) e = mc_window_energy<FMT>(a.x, row, a.T, n0 + s, a.N);   // prefix overflowed / NaN
         const double ew = a.mode == OFS_ZC_V2 ? (e > 1e-12 ? e : 1e-12)                 // zc_v2.py:268
                                               : (e > 0.0 ? e : 0.0) + 1e-12;            // zc.py:113-126
         const double inv = 1.0 / (a.ref_norm * sqrt(ew));
         const double2 r = make_double2(c.x * inv, c.y * inv);
         if (a.out) a.out[oi] = r;
-        if (a.mag) a.mag[oi] = sqrt(fma(r.x, r.x, r.y * r.y));
+        if (a.mag) a.mag[oi] = mf_cabs(r);
     }
 }
 
@@ -827,13 +853,16 @@ __global__ __launch_bounds__(MP_T) void mc_pers_kernel(McArgs a, const double2* 
 #if OFS_MP_AB & 4
             const double e = 1.0 + en[m];
 #else
-            const double e = P[mp_pq(o + 1)] - P[mp_pq(o + 1 - a.N)];   // sum |x|^2 over the N-sample window
+            const double phi = P[mp_pq(o + 1)];
+            double e = phi - P[mp_pq(o + 1 - a.N)];                     // sum |x|^2 over the N-sample window
+            if (!mc_finite(phi)) e = mc_window_energy<FMT>(a.x, row, a.T, n0 + s, a.N);   // prefix overflowed / NaN
 #endif
             const double ewc = a.mode == OFS_ZC_V2 ? (e > 1e-12 ? e : 1e-12)                 // zc_v2.py:268
                                                    : (e > 0.0 ? e : 0.0) + 1e-12;            // zc.py:113-126
             // 1 / (|ref| sqrt(e)) = rsqrt(e) / |ref| and |r| = s rsqrt(s), s = |r|^2: hardware rsqrt refined by
             // two Newton steps (an ulp or two from the reference's division and hypot, zc_v2.py:268-271)
-            const double inv = mp_rsqrt(ewc) * rn_inv;
+            // (a window whose energy is +inf gives 0, zc_v2.py:269-271: rsqrt(inf) = 0 would turn NaN in the steps)
+            const double inv = ewc <= MC_DBL_MAX ? mp_rsqrt(ewc) * rn_inv : 0.0;
             const double2 r = make_double2(c.x * inv, c.y * inv);
 #if OFS_MP_NTST                     // tuning builds: non-temporal output stores
             // (one 16-byte store per complex sample: a 2 x f64 vector, not two 8-byte halves)
@@ -943,7 +972,10 @@ __global__ __launch_bounds__(FX) void mc_extract_kernel(McArgs a) {
             const int64_t row = b * a.nb + br;
             const double2 c = a.U[(row * a.nblk + q) * a.M + (a.N - 1) + s];
             const double* P = pf + (size_t)br * plen;
-            const double e = P[pidx(s + a.N, per)] - P[pidx(s, per)];   // Σ |x|^2 over the N-sample window
+            const double phi = P[pidx(s + a.N, per)];
+            double e = phi - P[pidx(s, per)];                           // Σ |x|^2 over the N-sample window
+            if (!mc_finite(phi) && a.mode != OFS_ZC_RAW && a.mode != OFS_ZC_SUM)   // prefix overflowed / NaN
+                e = mc_window_energy<FMT>(a.x, row, a.T, n0 + s, a.N);
             if (a.mode == OFS_ZC_RAW) {
                 const int64_t o = row * a.nout + n0 + s;
                 if (a.out) a.out[o] = c;
